@@ -12,9 +12,11 @@ reference's own call-site argument construction (sgn_rast.step.render).  With N 
 the same Gaussians, renders its own (slightly yawed) view and the per-Gaussian gradients are
 all-reduced over RCCL inside the timed step (weak scaling: value = N*K / t).
 
-Rank 0 prints ONE JSON line with `roofline` (dominant kernel, HIP-event timed on its launch stream)
-and, at N=1, `cpu_baseline` (the repo's pure-PyTorch oracle rasterizer on the host cores, bounded
-sample).  Inputs are resident in HBM before the timed region starts.
+Rank 0 prints ONE JSON line: the headline (`value`, `ms_per_step` of exactly K timed steps).  With
+--full the line also carries `roofline` (dominant kernel, HIP-event timed on its launch stream), the
+extra lines, the `workloads` block and, at N=1, `cpu_baseline` (the repo's pure-PyTorch oracle
+rasterizer on the host cores).  --dump-outputs DIR writes what the last timed step computed.  Inputs
+are resident in HBM before the timed region starts.
 """
 from __future__ import annotations
 
@@ -118,6 +120,18 @@ def parse():
     ap.add_argument("--no-c4-extra", action="store_true",
                     help="N>1 / --force-dp: skip the extra line on the C4 scene (2 M Gaussians; north_star quotes its "
                          "8-GPU target there)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the first chunk without settle steps, "
+                         "the repeated chunks, the fused / caller-syncs / deferred-check / varying-camera / no-graph-proofs "
+                         "/ sort-ranking / C4 / forward-only lines, the per-kernel timing pass, walked entries and the "
+                         "roofline block, the scene-graph reducer check, the `workloads` block and the CPU baseline "
+                         "(--no-fused-extra, --no-workloads, --no-cpu-baseline, --no-c4-extra still switch their parts "
+                         "off).  Without it a run sets up, warms up, times the K steps, writes --dump-outputs and prints "
+                         "the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the LAST timed step computed (images, loss, projection "
+                         "outputs and parameter gradients; a fixed seeded row sample of the per-Gaussian arrays) as "
+                         "DIR/<name>.npy in float32 / float64, at most 64 MB in all")
     return ap.parse_args()
 
 
@@ -317,7 +331,7 @@ def cpu_baseline_bounded(args):
                 "sample": f"pure-PyTorch oracle did not finish its bounded sample within {args.cpu_timeout:.0f}s"}
 
 
-WORKLOADS = [   # name, extra flags (each run adds --no-cpu-baseline --no-fused-extra --no-workloads --steps K --warmup W)
+WORKLOADS = [   # name, extra flags (each run adds --full --no-cpu-baseline --no-fused-extra --no-workloads --steps K --warmup W)
     ("c2", ["--scene", "c2"]),                                       # BASELINE.json configs[1]: 500 k Gaussians
     ("c4_one_gpu", ["--scene", "c4"]),                               # configs[3]'s scene (2 M Gaussians) on ONE GPU
     ("street", ["--street"]),
@@ -344,7 +358,7 @@ def run_workloads(args, budget_s):
         if time.perf_counter() - t_start > budget_s:
             out[name] = {"value": None, "skipped": f"the workloads block's budget of {budget_s:.0f} s was spent"}
             continue
-        cmd = [sys.executable, os.path.abspath(__file__), "--no-cpu-baseline", "--no-fused-extra", "--no-workloads",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-cpu-baseline", "--no-fused-extra", "--no-workloads",
                "--steps", str(args.steps), "--warmup", str(args.warmup), "--settle", str(args.settle)] + flags
         t0 = time.perf_counter()
         try:
@@ -378,11 +392,112 @@ def run_workloads(args, budget_s):
     return out
 
 
+DUMP_LIMIT_BYTES = 60_000_000   # --dump-outputs: payload bound (the .npy headers come on top; the contract says 64 MB)
+DUMP_ROWS = 32768               # per-Gaussian arrays: rows sampled per model (scaled down for the scene graph's nine)
+
+
+def _sample_index(n: int, k: int, seed: int):
+    """A fixed, seeded, sorted sample of k of n rows (None: keep all n)."""
+    if n <= k:
+        return None
+    return torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:k].sort().values
+
+
+def collect_outputs(out, models, cam, sky=None) -> dict:
+    """--dump-outputs: host copies of what a step handed its caller, {name: numpy array}.  `out` is the step's namespace
+    (images, projection outputs, loss), `models` the parameter dicts whose `.grad` the backward filled.  Per-Gaussian
+    arrays (and the sky cube map's gradient) keep the same seeded row sample, stored beside them as `rows*`; the images
+    are kept whole when they fit in what is left of DUMP_LIMIT_BYTES, else as a seeded pixel sample (`pixels`).  float32,
+    the loss and the sample indices float64."""
+    import numpy as np
+    H, W = cam.height, cam.width
+    arrays, used = {}, 0
+
+    def put(name, t, dtype=np.float32):
+        nonlocal used
+        a = t.detach().cpu().numpy().astype(dtype)
+        arrays[name] = a
+        used += a.nbytes
+
+    n_tot = sum(int(m["means"].shape[0]) for m in models)
+    rows_per = max(1024, DUMP_ROWS // len(models))
+    idx_tot = _sample_index(n_tot, rows_per, 0)
+    if idx_tot is not None:
+        put("rows", idx_tot, np.float64)
+    images, scalars = {}, {}
+    for name, v in sorted(vars(out).items()):
+        if not isinstance(v, torch.Tensor):
+            continue
+        if v.dim() >= 3 and v.shape[0] == 1:
+            v = v[0]                       # (a batch of one image, as the sky lookup returns it)
+        if v.dim() >= 2 and tuple(v.shape[:2]) == (H, W):
+            images[name] = v
+        elif v.numel() == 1:
+            scalars[name] = v
+        elif v.dim() >= 1 and v.shape[0] == n_tot:
+            put(name, v if idx_tot is None else v[idx_tot.to(v.device)])
+        else:
+            images[name] = v               # (none on the bench's paths; sampled with the images if they do not fit)
+    for name, v in scalars.items():
+        put(name, v.reshape(()), np.float64)
+    for i, m in enumerate(models):
+        idx = idx_tot if len(models) == 1 else _sample_index(int(m["means"].shape[0]), rows_per, 1 + i)
+        if len(models) > 1 and idx is not None:
+            put(f"rows_m{i}", idx, np.float64)
+        for k, p in m.items():
+            if p.grad is not None:
+                put(f"grad_{k}" if len(models) == 1 else f"grad_m{i}_{k}",
+                    p.grad if idx is None else p.grad[idx.to(p.grad.device)])
+    if sky is not None and sky["base"].grad is not None:
+        g = sky["base"].grad.reshape(-1, sky["base"].shape[-1])
+        idx = _sample_index(g.shape[0], DUMP_ROWS, 101)
+        put("grad_sky_base", g if idx is None else g[idx.to(g.device)])
+        if idx is not None:
+            put("rows_sky", idx, np.float64)
+    flat = {n: v.reshape(H * W, -1) if v.dim() >= 2 and tuple(v.shape[:2]) == (H, W) else
+            v.reshape(-1, v.shape[-1] if v.dim() >= 2 else 1) for n, v in images.items()}
+    if sum(v.numel() * 4 for v in flat.values()) <= DUMP_LIMIT_BYTES - used:
+        for n, v in images.items():
+            put(n, v)
+    else:
+        # one sample per row count (the pixels of all images alike), each sampled row costing its float32 values in
+        # every array of that row count plus its float64 index
+        row_bytes = {}
+        for v in flat.values():
+            row_bytes[v.shape[0]] = row_bytes.get(v.shape[0], 8) + 4 * v.shape[1]
+        frac = (DUMP_LIMIT_BYTES - used) / sum(r * b for r, b in row_bytes.items())
+        picks = {}
+        for n, v in flat.items():
+            r = v.shape[0]
+            if r not in picks:
+                picks[r] = _sample_index(r, max(1, int(r * frac)), 201 + len(picks))
+                if picks[r] is not None:
+                    put("pixels" if r == H * W else f"{n}_rows", picks[r], np.float64)
+            put(n, v if picks[r] is None else v[picks[r].to(v.device)])
+    assert used <= DUMP_LIMIT_BYTES, used
+    return arrays
+
+
+def write_outputs(dirname: str, arrays: dict) -> dict:
+    """DIR/<name>.npy for every array of collect_outputs(); returns {name: shape}."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for n, a in arrays.items():
+        np.save(os.path.join(dirname, n + ".npy"), a)
+    return {n: list(a.shape) for n, a in arrays.items()}
+
+
+def dump_outputs(dirname: str, out, models, cam, sky=None) -> dict:
+    """--dump-outputs of one step: collect_outputs() written as DIR/<name>.npy; returns {name: shape}."""
+    return write_outputs(dirname, collect_outputs(out, models, cam, sky))
+
+
 _on_failure = [None]      # set by main() for N-rank runs: prints the kept headline line (or the error line) and exits
 
 
 def main():
     args = parse()
+    full = args.full         # everything beside the headline (the plain run: set-up, warm-up, K timed steps, the line)
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline(args.scene, args.n, args.cpu_rows, args.cpu_frac)), flush=True)
         return
@@ -566,6 +681,7 @@ def main():
         else:
             loss = ((out.rgb * w_img).sum() + (out.alpha * w_a).sum() + (out.object_acc * w_a).sum()) / n_pix
         loss.backward()
+        out.loss = loss.detach()
         if reducer is not None:
             reducer.finish()
         if adam is not None:
@@ -685,14 +801,20 @@ def main():
     # reported beside the headline as `without_settle_steps`; the headline itself follows with the settle steps in front
     # (for which this first measurement has then done part of the settling: the later figure is the steady one either way)
     literal = None
-    if args.settle > 0 and world == 1 and not force_dp:
+    if full and args.settle > 0 and world == 1 and not force_dp:
         dt0, _ = measure_headline(0)
         literal = {"value": args.steps / dt0, "unit": "images/sec", "ms_per_step": 1e3 * dt0 / args.steps,
                    "note": f"the contract's letter: exactly {args.warmup} warm-up steps, then {args.steps} timed steps, "
                            "straight after the host-side set-up (no settle steps): on some boxes a device that idled through "
                            "the set-up runs this first chunk up to 30 % slow (profiles/r05aa_settle_ab.log)"}
     dt, out = measure_headline(args.settle)
+    # --dump-outputs: host copies of the last timed step's results, taken right after each measurement, so that the
+    # files hold the step of the measurement the headline reports
+    want_dump = bool(args.dump_outputs) and rank == 0
+    step_models = [P] if sg is None else sg[0]
+    outputs = collect_outputs(out, step_models, cam, sky) if want_dump else None
     if safe_first:
+        outputs_safe = outputs
         dt_safe, safe_reducer = dt, reducer
         kept["line"] = headline_line(dt_safe, f"dp{world} (view-parallel; {exchange_name(True)})")
         watchdog.seconds = min(watchdog.seconds, 30.0)     # a step is milliseconds; the fallback line is in hand
@@ -711,6 +833,7 @@ def main():
             raise RuntimeError(f"optimised exchange disagrees with the dense all-reduce: rel-L2 {worst:.3e}")
         del ref
         dt_opt, out = measure_headline(0)
+        outputs = collect_outputs(out, step_models, cam, sky) if want_dump else None
         dp_paths = {"dense_after_backward": {"value": world * args.steps / dt_safe, "ms_per_step": 1e3 * dt_safe / args.steps},
                     "optimised": {"value": world * args.steps / dt_opt, "ms_per_step": 1e3 * dt_opt / args.steps,
                                   "exchange": exchange_name(False), "grad_rel_l2_vs_dense": worst},
@@ -721,18 +844,21 @@ def main():
             if reducer.sh_exchange is not None:
                 reducer.sh_exchange.remove()
             reducer.remove()
-            reducer, dt = safe_reducer, dt_safe
+            reducer, dt, outputs = safe_reducer, dt_safe, outputs_safe
         kept["line"] = headline_line(dt, f"dp{world} (view-parallel; {exchange_name(reducer is safe_reducer)})")
         kept["line"]["config"]["dp"] = {"paths": dp_paths}
     elif world > 1:
         kept["line"] = headline_line(dt, f"dp{world} (view-parallel; {exchange_name(False)})")
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs)
+        del outputs
     n_isect = int(out.num_tiles_hit.sum().item())
-    repeat = repeat_chunks(dt)
+    repeat = repeat_chunks(dt) if full else None
 
     # scene graph under the N-rank harness: the reducer's gradients against plain per-tensor all-reduces of the same
     # step's local gradients (SUM, divided on the device) — nothing but `all_reduce`, issued after the backward
     sg_check = None
-    if sg is not None and reducer is not None:
+    if full and sg is not None and reducer is not None:
         held, reducer = reducer, None
         with held.suspended():            # (a backward that is not a step of the reducer: its hooks stay idle)
             one_step()
@@ -752,7 +878,7 @@ def main():
 
     # the same function through the fused front ends (extension API), reported beside the headline
     fused_extra = None
-    if args.path == "dropin" and not args.no_fused_extra:
+    if full and args.path == "dropin" and not args.no_fused_extra:
         for _ in range(max(2, args.warmup // 2)):
             one_step(True)
         gc.collect()
@@ -789,7 +915,7 @@ def main():
     # the same drop-in step (a) with the two host syncs the reference's model code makes around the operators, on top
     # of the library defaults, and (b) with the opt-in deferred argument check
     sync_extra = deferred_extra = vary_extra = None
-    if args.path == "dropin" and sg is None and not args.caller_syncs and not args.no_fused_extra:
+    if full and args.path == "dropin" and sg is None and not args.caller_syncs and not args.no_fused_extra:
         h0 = dict(ops.binning_stats)
         vary_extra = timed_variant(vary_camera=True)
         vary_extra["speculative_hits"] = ops.binning_stats["speculative_hits"] - h0["speculative_hits"]
@@ -814,7 +940,7 @@ def main():
     # the PORTABLE number (VERDICT r03 #6a): the same drop-in step with every graph proof switched off — what the step
     # costs when the autograd graph behind the operators' arguments is not the reference's (or not recognised)
     no_proofs_extra = None
-    if args.path == "dropin" and not args.no_fused_extra:
+    if full and args.path == "dropin" and not args.no_fused_extra:
         saved_p = (ops.activation_proofs, ops.sh_split_backward)
         ops.activation_proofs = ops.sh_split_backward = False
         try:
@@ -827,7 +953,7 @@ def main():
     # what the documented (default) sort ranking costs: the same step with the returning-atomic ranking forced, if
     # this device passes the probe under load (the line's `value` is measured with the default)
     sort_ab = None
-    if args.path == "dropin" and not args.no_fused_extra and world == 1 and L.sort_rank_mode() == 0:
+    if full and args.path == "dropin" and not args.no_fused_extra and world == 1 and L.sort_rank_mode() == 0:
         try:
             bad = L.sort_selftest_under_load(rounds=64)
             if bad == 0:
@@ -843,8 +969,8 @@ def main():
 
     # north_star quotes the 8-GPU target on C4 (2 M Gaussians): the same harness on that scene, beside the headline
     c4_extra = None
-    if (world > 1 or force_dp) and args.scene == "metric" and sg is None and sky is None and not args.no_c4_extra \
-            and not args.street and not args.translucent and not args.n:
+    if full and (world > 1 or force_dp) and args.scene == "metric" and sg is None and sky is None \
+            and not args.no_c4_extra and not args.street and not args.translucent and not args.n:
         from sgn_rast import fused as fused_
         keep = (P, cam, w_img, w_a, reducer, ring)
         hooks = (ops._sh_exchange, fused_._sh_exchange, ops._touch_sink)      # the kept reducer's taps: put aside
@@ -872,7 +998,7 @@ def main():
     # no_grad: projection, SH at full degree, rgb+alpha pass AND the depth pass (sgn_splatfacto.py:982-996 runs in eval
     # too); the rgb-only figure beside it
     eval_extra = None
-    if sg is None and not args.no_fused_extra:
+    if full and sg is None and not args.no_fused_extra:
         def fwd_only(with_depth, fused=False):
             if watchdog is not None:
                 watchdog.beat()
@@ -910,16 +1036,18 @@ def main():
     # per-kernel HIP-event spans (library brackets each launch on its own stream), separate short pass.  The forward-only
     # lines above rendered depth, which taught the "auto" depth-channel policy to accumulate the fourth channel; the
     # headline step renders none, so the policy is put back to where the timed loop had it.
-    if not args.with_depth and sg is None:
-        ops._depth_state.update(want=False, unused=0)
-    L.timing_enable(True)
-    k_steps = max(3, min(args.steps, 10))
-    for _ in range(k_steps):
-        one_step()
-    torch.cuda.synchronize()
-    rep = L.timing_report()
-    L.timing_enable(False)
-    kernels = {k: (c, (t / c if c else 0.0)) for k, (c, t) in rep.items()}  # avg ms per launch
+    kernels = None
+    if full:
+        if not args.with_depth and sg is None:
+            ops._depth_state.update(want=False, unused=0)
+        L.timing_enable(True)
+        k_steps = max(3, min(args.steps, 10))
+        for _ in range(k_steps):
+            one_step()
+        torch.cuda.synchronize()
+        rep = L.timing_report()
+        L.timing_enable(False)
+        kernels = {k: (c, (t / c if c else 0.0)) for k, (c, t) in rep.items()}  # avg ms per launch
     if watchdog is not None:
         watchdog.stop()      # every collective of the run is behind us; what follows is rank-local (CPU baseline ...)
     if reducer is not None:
@@ -932,7 +1060,7 @@ def main():
     # WALKED before the tiles saturate (the backward's reverse walk starts at the deepest composited position the
     # forward recorded per tile), (entry, quadrant) pairs the forward evaluated
     walk = None
-    if sg is None and rank == 0:
+    if full and sg is None and rank == 0:
         ops.clear_binning_cache()
         o_ = step.render(P, cam, 3, 16, caller_syncs=False) if args.path == "dropin" else step.render_fused(P, cam, 3, 16)
         node = o_.rgb.grad_fn
@@ -947,112 +1075,103 @@ def main():
 
     if rank == 0:
         n_pix = cam.height * cam.width
-        # dominant single kernel (the "sort" slot spans 18 launches, so it is not a candidate)
-        dom = max(("raster_bwd", "raster_fwd", "pack_records"), key=lambda k: kernels[k][1])
-        dur_s = kernels[dom][1] * 1e-3
-        # SURVEY.md section 8d's per-unit bytes of the dominant kernel: per list entry / per pixel
-        bytes_per_entry = {"raster_bwd": 112, "raster_fwd": 40, "pack_records": 40}[dom]   # gather 40 (+ grad scatter 72)
-        pix_bytes = {"raster_bwd": 24, "raster_fwd": 20, "pack_records": 0}[dom]
-        # (1) THE ROOFLINE FIGURE: bytes of the units the launch PROCESSES — the list entries it
-        # walks before its tile saturates (the forward stops at T <= 1e-4, the backward starts at final_idx: reference
-        # semantics), plus the per-pixel bytes — over the launch time.  Cannot exceed the measured traffic, let alone 1.
-        processed = None
-        if walk is not None and dur_s > 0:
-            n_units = walk["entries_walked"] if dom != "pack_records" else n_gauss
-            processed = bytes_per_entry * n_units + pix_bytes * n_pix
-        achieved = processed / dur_s / 1e9 if processed is not None else None
-        # (2) the section-8d BUDGET: every upstream-semantic intersection charged, whether or not a tile still walks it.
-        # A rate at which the reference's byte budget is retired; > 1 where tiles saturate early; NOT a utilisation.
-        budget = bytes_per_entry * n_isect + pix_bytes * n_pix
-        step_bytes = 748 * n_gauss + 316 * n_isect + 44 * n_pix
-        # (3) counters: separate rocprofv3 passes (they cannot be read from inside this process), kept per kernel and
-        # workload in profiles/roofline_pmc.json with the source tables, the git head and the hash of raster.hip they
-        # were taken on; a different raster.hip marks them STALE and they are not replayed as this run's.
-        import hashlib
-        workload_key = ("scene_graph_" + args.path if sg is not None else "street" if args.street else
-                        args.scene if not (args.n or args.translucent or args.sky) else None)
-        traffic, pmc, pmc_info = None, None, {"file": "profiles/roofline_pmc.json"}
-        slots_measured = None
-        try:
-            pj = json.load(open(os.path.join(ROOT, "profiles", "roofline_pmc.json")))
-            here = hashlib.sha256(open(os.path.join(ROOT, "street-gaussians-ns_amd", "csrc", "raster.hip"), "rb").read()).hexdigest()
-            pmc_info.update(round=pj.get("round"), git_head=pj.get("git_head"),
-                            stale=pj.get("raster_hip_sha256") != here)
-            wl = (pj.get("workloads") or {}).get(workload_key) if workload_key else None
-            if wl is not None and not pmc_info["stale"]:
-                slots_measured = wl.get("slots")
-            if wl is not None and dom in wl and not pmc_info["stale"]:
-                pmc = wl[dom]
-                traffic = pmc.get("hbm_traffic_bytes")
-        except Exception as e:
-            pmc_info["error"] = repr(e)
-        roof_extra = {"pmc": pmc_info}
-        if walk is not None:
-            roof_extra["walked"] = dict(walk)
-        if traffic is not None and dur_s > 0:
-            roof_extra["hbm_measured"] = {"traffic_bytes": traffic, "GBps": traffic / dur_s / 1e9,
-                                          "frac": traffic / dur_s / 1e9 / HBM_PEAK_GBS, "source": pmc.get("hbm_source"),
-                                          "traffic_over_processed": traffic / processed if processed else None}
-        if (pmc is not None and "valu" in pmc and walk is not None and dur_s > 0
-                and pmc["valu"].get("valu_insts_per_pair") is not None):
-            v = pmc["valu"]
-            # live part: this run's launch duration and pair count; PMC part: instructions per evaluated pair, the
-            # mix-weighted issue cycles per wave-instruction (calibrated microbenchmark) and the profiled clock
-            pairs = walk["quadrant_pairs_evaluated_fwd"]
-            insts = v["valu_insts_per_pair"] * pairs
-            simd_cycles = v["simds"] * v["clock_ghz"] * 1e9 * dur_s
-            roof_extra["valu"] = {"pair_evaluations": pairs, "valu_insts_per_pair": v["valu_insts_per_pair"],
-                                  "valu_wave_insts_per_launch": insts,
-                                  "issue_cycles_per_inst": v["issue_cycles_per_inst"],
-                                  "issue_cycle_frac": insts * v["issue_cycles_per_inst"] / simd_cycles,
-                                  "active_counter_vs_saturated_mix": v.get("counter_frac_calibrated"),
-                                  "source": v.get("source")}
-        # (4) every library kernel of the step against the HBM roofline: algorithmic bytes of THIS pipeline per step
-        # (DESIGN.md section 6 lists the per-unit figures) / the slot's event-timed device time per step / 8 TB/s
-        per_kernel = None
-        if walk is not None:
-            Ic, Wk = walk["pairs_listed"], walk["entries_walked"]
-            alg_step = {"project_fwd": 100 * n_gauss, "project_bwd": 188 * n_gauss, "sh_fwd": 216 * n_gauss,
-                        "sh_bwd": 216 * n_gauss, "scan": 16 * n_gauss,
-                        "map_isect": (76 + 40) * n_gauss + 6 * Ic,                      # count pass + emission
-                        "sort": (24 + 3 * 20) * n_gauss + 2 * (2 + 12) * Ic,            # depth rank + tile sort
-                        "tile_bins": 2 * Ic, "pack_records": 88 * n_gauss, "unpack_grads": 84 * n_gauss,
-                        "raster_fwd": 40 * Wk + 20 * n_pix, "raster_bwd": 112 * Wk + 24 * n_pix}
-            per_kernel = {}
-            for k_, (cnt_, avg_) in kernels.items():
-                if cnt_ and k_ in alg_step:
-                    ms_ = cnt_ * avg_ / k_steps
-                    per_kernel[k_] = {"ms_per_step": round(ms_, 4), "launch_brackets_per_step": round(cnt_ / k_steps, 2),
-                                      "alg_MB_per_step": round(alg_step[k_] / 1e6, 2),
-                                      "hbm_frac": round(alg_step[k_] / (ms_ * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
-                    # measured HBM traffic of the slot's kernels (rocprofv3 FETCH_SIZE x 2 + WRITE_SIZE, replayed from
-                    # profiles/roofline_pmc.json while its stamp matches this raster.hip): traffic above the algorithmic
-                    # bytes = re-reads
-                    m_ = (slots_measured or {}).get(k_)
-                    if m_ is not None:
-                        per_kernel[k_]["hbm_MB_measured"] = round(m_["hbm_bytes_per_step"] / 1e6, 2)
-                        per_kernel[k_]["measured_over_alg"] = round(m_["hbm_bytes_per_step"] / alg_step[k_], 3)
-        measured_bound = (pmc or {}).get("bound")
-        if sg is not None:
-            # the scene graph's raster slots average launches over DIFFERENT lists (main pass, accumulation walks, group
-            # walks): no single per-launch byte count describes them, and the section-8d budget of one pass printed over
-            # that average was the "1.007 of peak" of round 4 — the per-launch figures of this workload are in the kernel
-            # trace and counter tables under profiles/ (r05_*_sg_*), not in this line
-            budget = None
-        line = {
-            "metric": "train-step images/sec (fwd+bwd) @1M Gaussians 1920x1280",
-            "value": world * args.steps / dt, "unit": "images/sec", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": (f"{args.scene}: {n_gauss} Gaussians, {cam.width}x{cam.height}, SH deg 3 (K=16), "
-                                    f"block 16, fwd+bwd{' + depth pass' if args.with_depth else ''}; "
-                                    f"measured I={n_isect} tile intersections/view"),
-                       "parallelism": (f"dp{world} (view-parallel; {exchange_name(safe_reducer is not None and reducer is safe_reducer)})"
-                                       if world > 1 else "single"),
-                       "n_gaussians": n_gauss, "n_isect": n_isect},
+        roofline = None
+        if full:
+            # dominant single kernel (the "sort" slot spans 18 launches, so it is not a candidate)
+            dom = max(("raster_bwd", "raster_fwd", "pack_records"), key=lambda k: kernels[k][1])
+            dur_s = kernels[dom][1] * 1e-3
+            # SURVEY.md section 8d's per-unit bytes of the dominant kernel: per list entry / per pixel
+            bytes_per_entry = {"raster_bwd": 112, "raster_fwd": 40, "pack_records": 40}[dom]   # gather 40 (+ grad scatter 72)
+            pix_bytes = {"raster_bwd": 24, "raster_fwd": 20, "pack_records": 0}[dom]
+            # (1) THE ROOFLINE FIGURE: bytes of the units the launch PROCESSES — the list entries it
+            # walks before its tile saturates (the forward stops at T <= 1e-4, the backward starts at final_idx: reference
+            # semantics), plus the per-pixel bytes — over the launch time.  Cannot exceed the measured traffic, let alone 1.
+            processed = None
+            if walk is not None and dur_s > 0:
+                n_units = walk["entries_walked"] if dom != "pack_records" else n_gauss
+                processed = bytes_per_entry * n_units + pix_bytes * n_pix
+            achieved = processed / dur_s / 1e9 if processed is not None else None
+            # (2) the section-8d BUDGET: every upstream-semantic intersection charged, whether or not a tile still walks it.
+            # A rate at which the reference's byte budget is retired; > 1 where tiles saturate early; NOT a utilisation.
+            budget = bytes_per_entry * n_isect + pix_bytes * n_pix
+            step_bytes = 748 * n_gauss + 316 * n_isect + 44 * n_pix
+            # (3) counters: separate rocprofv3 passes (they cannot be read from inside this process), kept per kernel and
+            # workload in profiles/roofline_pmc.json with the source tables, the git head and the hash of raster.hip they
+            # were taken on; a different raster.hip marks them STALE and they are not replayed as this run's.
+            import hashlib
+            workload_key = ("scene_graph_" + args.path if sg is not None else "street" if args.street else
+                            args.scene if not (args.n or args.translucent or args.sky) else None)
+            traffic, pmc, pmc_info = None, None, {"file": "profiles/roofline_pmc.json"}
+            slots_measured = None
+            try:
+                pj = json.load(open(os.path.join(ROOT, "profiles", "roofline_pmc.json")))
+                here = hashlib.sha256(open(os.path.join(ROOT, "street-gaussians-ns_amd", "csrc", "raster.hip"), "rb").read()).hexdigest()
+                pmc_info.update(round=pj.get("round"), git_head=pj.get("git_head"),
+                                stale=pj.get("raster_hip_sha256") != here)
+                wl = (pj.get("workloads") or {}).get(workload_key) if workload_key else None
+                if wl is not None and not pmc_info["stale"]:
+                    slots_measured = wl.get("slots")
+                if wl is not None and dom in wl and not pmc_info["stale"]:
+                    pmc = wl[dom]
+                    traffic = pmc.get("hbm_traffic_bytes")
+            except Exception as e:
+                pmc_info["error"] = repr(e)
+            roof_extra = {"pmc": pmc_info}
+            if walk is not None:
+                roof_extra["walked"] = dict(walk)
+            if traffic is not None and dur_s > 0:
+                roof_extra["hbm_measured"] = {"traffic_bytes": traffic, "GBps": traffic / dur_s / 1e9,
+                                              "frac": traffic / dur_s / 1e9 / HBM_PEAK_GBS, "source": pmc.get("hbm_source"),
+                                              "traffic_over_processed": traffic / processed if processed else None}
+            if (pmc is not None and "valu" in pmc and walk is not None and dur_s > 0
+                    and pmc["valu"].get("valu_insts_per_pair") is not None):
+                v = pmc["valu"]
+                # live part: this run's launch duration and pair count; PMC part: instructions per evaluated pair, the
+                # mix-weighted issue cycles per wave-instruction (calibrated microbenchmark) and the profiled clock
+                pairs = walk["quadrant_pairs_evaluated_fwd"]
+                insts = v["valu_insts_per_pair"] * pairs
+                simd_cycles = v["simds"] * v["clock_ghz"] * 1e9 * dur_s
+                roof_extra["valu"] = {"pair_evaluations": pairs, "valu_insts_per_pair": v["valu_insts_per_pair"],
+                                      "valu_wave_insts_per_launch": insts,
+                                      "issue_cycles_per_inst": v["issue_cycles_per_inst"],
+                                      "issue_cycle_frac": insts * v["issue_cycles_per_inst"] / simd_cycles,
+                                      "active_counter_vs_saturated_mix": v.get("counter_frac_calibrated"),
+                                      "source": v.get("source")}
+            # (4) every library kernel of the step against the HBM roofline: algorithmic bytes of THIS pipeline per step
+            # (DESIGN.md section 6 lists the per-unit figures) / the slot's event-timed device time per step / 8 TB/s
+            per_kernel = None
+            if walk is not None:
+                Ic, Wk = walk["pairs_listed"], walk["entries_walked"]
+                alg_step = {"project_fwd": 100 * n_gauss, "project_bwd": 188 * n_gauss, "sh_fwd": 216 * n_gauss,
+                            "sh_bwd": 216 * n_gauss, "scan": 16 * n_gauss,
+                            "map_isect": (76 + 40) * n_gauss + 6 * Ic,                      # count pass + emission
+                            "sort": (24 + 3 * 20) * n_gauss + 2 * (2 + 12) * Ic,            # depth rank + tile sort
+                            "tile_bins": 2 * Ic, "pack_records": 88 * n_gauss, "unpack_grads": 84 * n_gauss,
+                            "raster_fwd": 40 * Wk + 20 * n_pix, "raster_bwd": 112 * Wk + 24 * n_pix}
+                per_kernel = {}
+                for k_, (cnt_, avg_) in kernels.items():
+                    if cnt_ and k_ in alg_step:
+                        ms_ = cnt_ * avg_ / k_steps
+                        per_kernel[k_] = {"ms_per_step": round(ms_, 4), "launch_brackets_per_step": round(cnt_ / k_steps, 2),
+                                          "alg_MB_per_step": round(alg_step[k_] / 1e6, 2),
+                                          "hbm_frac": round(alg_step[k_] / (ms_ * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+                        # measured HBM traffic of the slot's kernels (rocprofv3 FETCH_SIZE x 2 + WRITE_SIZE, replayed from
+                        # profiles/roofline_pmc.json while its stamp matches this raster.hip): traffic above the algorithmic
+                        # bytes = re-reads
+                        m_ = (slots_measured or {}).get(k_)
+                        if m_ is not None:
+                            per_kernel[k_]["hbm_MB_measured"] = round(m_["hbm_bytes_per_step"] / 1e6, 2)
+                            per_kernel[k_]["measured_over_alg"] = round(m_["hbm_bytes_per_step"] / alg_step[k_], 3)
+            measured_bound = (pmc or {}).get("bound")
+            if sg is not None:
+                # the scene graph's raster slots average launches over DIFFERENT lists (main pass, accumulation walks, group
+                # walks): no single per-launch byte count describes them, and the section-8d budget of one pass printed over
+                # that average was the "1.007 of peak" of round 4 — the per-launch figures of this workload are in the kernel
+                # trace and counter tables under profiles/ (r05_*_sg_*), not in this line
+                budget = None
             # roofline: bound "hbm" is the roofline the fraction is priced against (north_star:
             # achieved fraction of the HBM roofline); `limiter` is what the counters say holds the kernel (VALU issue).
-            "roofline": dict({"bound": "hbm", "limiter": measured_bound or "valu (see DESIGN.md section 4)", "kernel": dom,
+            roofline = dict({"bound": "hbm", "limiter": measured_bound or "valu (see DESIGN.md section 4)", "kernel": dom,
                               "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                               "frac": (achieved / HBM_PEAK_GBS) if achieved is not None else None,
                               "frac_is": "bytes of the units the launch PROCESSES (list entries walked before their tile "
@@ -1067,10 +1186,23 @@ def main():
                                                       "early; NOT a utilisation"},
                               "step_alg_bytes_8d": step_bytes,
                               "step_budget_over_peak": step_bytes / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
-                              "per_kernel": per_kernel}, **roof_extra),
-            "kernels_avg_ms": {k: round(v[1], 4) for k, v in kernels.items()},
-            "repeat": repeat,
+                              "per_kernel": per_kernel}, **roof_extra)
+        line = {
+            "metric": "train-step images/sec (fwd+bwd) @1M Gaussians 1920x1280",
+            "value": world * args.steps / dt, "unit": "images/sec", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": (f"{args.scene}: {n_gauss} Gaussians, {cam.width}x{cam.height}, SH deg 3 (K=16), "
+                                    f"block 16, fwd+bwd{' + depth pass' if args.with_depth else ''}; "
+                                    f"measured I={n_isect} tile intersections/view"),
+                       "parallelism": (f"dp{world} (view-parallel; {exchange_name(safe_reducer is not None and reducer is safe_reducer)})"
+                                       if world > 1 else "single"),
+                       "n_gaussians": n_gauss, "n_isect": n_isect},
+            "roofline": roofline,
         }
+        if full:
+            line["kernels_avg_ms"] = {k: round(v[1], 4) for k, v in kernels.items()}
+            line["repeat"] = repeat
         line["config"]["path"] = args.path
         if world > 1 or force_dp:
             line["config"]["backend"] = torch.distributed.get_backend()
@@ -1100,7 +1232,8 @@ def main():
                                    f"steps (`--settle 0` = the contract's letter): a device that idled through the "
                                    "host-side set-up ran the first 20-step chunk 30 % slow on some boxes "
                                    "(profiles/r05aa_settle_ab.log); the timed region is exactly K steps between the two "
-                                   "barrier + synchronize pairs, and `repeat` holds further chunks of exactly K steps")
+                                   "barrier + synchronize pairs" + (", and `repeat` holds further chunks of exactly K "
+                                                                    "steps" if full else ""))
         if literal is not None:
             line["without_settle_steps"] = literal
         from sgn_rast import config as sgn_config
@@ -1155,11 +1288,11 @@ def main():
         plain_run = (world == 1 and not force_dp and args.scene == "metric" and args.path == "dropin" and sg is None
                      and sky is None and not (args.street or args.translucent or args.n or args.with_depth
                                               or args.photometric or args.adam or args.caller_syncs))
-        if plain_run and not args.no_workloads:
+        if full and plain_run and not args.no_workloads:
             # the device is free from here on (nothing of this process is queued): the other workloads run one by one
             torch.cuda.synchronize()
             line["workloads"] = run_workloads(args, args.workloads_budget)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline_bounded(args)
             except Exception as e:  # the GPU number stands on its own

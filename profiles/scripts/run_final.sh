@@ -1,5 +1,12 @@
-mkdir -p gpurun_out
-timeout 1200 python -m pytest tests -m gpu -x -q > gpurun_out/pytest_gpu_final.log 2>&1; echo "pytest rc=$?" >> gpurun_out/pytest_gpu_final.log
-grep -E "passed|failed|rc=" gpurun_out/pytest_gpu_final.log | tail -3
-timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-timeout 600 python bench.py > gpurun_out/bench_final.json 2> gpurun_out/bench_final.err; tail -c 1500 gpurun_out/bench_final.json
+# GPU suite, smoke, the --full bench line; output under $1 (bench_out).  Each GPU step has its own time limit and the
+# first one that fails ends the script: nothing more is started on the card.
+set -o pipefail
+O=${1:-bench_out}
+mkdir -p $O
+timeout -k 10 1200 python -m pytest tests -m gpu -x -q > $O/pytest_gpu_final.log 2>&1; rc=$?
+echo "pytest rc=$rc" >> $O/pytest_gpu_final.log
+grep -E "passed|failed|rc=" $O/pytest_gpu_final.log | tail -3
+[ $rc -eq 0 ] || exit $rc
+timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 || exit $?
+timeout -k 10 600 python bench.py --full > $O/bench_final.json 2> $O/bench_final.err || exit $?
+tail -c 1500 $O/bench_final.json

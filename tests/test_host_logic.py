@@ -158,6 +158,53 @@ def test_bench_cpu_baseline_leg_runs_without_a_gpu():
     assert d["c_port_all_cores"]["cores"] >= 1 and d["c_port_all_cores"]["value"] > 0
 
 
+def test_bench_dump_outputs_is_bounded_and_reproducible(tmp_path, monkeypatch):
+    """bench.py --dump-outputs on outputs of the metric size (1 M Gaussians, 1920x1280) and of the scene graph (nine
+    models, five images, the sky cube map's gradient): float32 / float64 files, at most 64 MB in all, the same seeded
+    samples every time."""
+    import os
+    import sys
+    from types import SimpleNamespace
+    import numpy as np
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    # (importing bench.py sets this variable for its own process: put back as it was after the test)
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
+    import bench
+    H, W, N = 1280, 1920, 1_000_000
+    cam = SimpleNamespace(height=H, width=W)
+    g = torch.Generator().manual_seed(3)
+
+    def leaf(*shape):
+        p = torch.zeros(*shape, requires_grad=True)
+        p.grad = torch.rand(*shape, generator=g)
+        return p
+
+    P = {k: leaf(N, *s) for k, s in dict(means=(3,), log_scales=(3,), quats=(4,), opacity_logits=(1,),
+                                         features_dc=(1, 3), features_rest=(15, 3)).items()}
+    out = SimpleNamespace(rgb=torch.rand(H, W, 3, generator=g), alpha=torch.rand(H, W, generator=g),
+                          xys=torch.rand(N, 2, generator=g), radii=torch.randint(0, 9, (N,), dtype=torch.int32),
+                          loss=torch.tensor(0.25))
+    models = [{"means": leaf(N // 9, 3), "features_rest": leaf(N // 9, 15, 3)} for _ in range(9)]
+    sg_out = SimpleNamespace(rgb=out.rgb, alpha=out.alpha, depth=torch.rand(H, W, 1, generator=g),
+                             object_acc=out.alpha, background_acc=out.alpha, loss=out.loss,
+                             radii=torch.zeros(9 * (N // 9), dtype=torch.int32))
+    sky = {"base": leaf(6, 1024, 1024, 3)}
+    for name, args in (("plain", (out, [P], cam)), ("scene_graph", (sg_out, models, cam, sky))):
+        shapes = [bench.dump_outputs(str(tmp_path / f"{name}{i}"), *args) for i in range(2)]
+        assert shapes[0] == shapes[1]
+        files = sorted(os.listdir(tmp_path / f"{name}0"))
+        assert files == sorted(n + ".npy" for n in shapes[0])
+        assert sum(os.path.getsize(tmp_path / f"{name}0" / f) for f in files) <= 64 * 10**6
+        for f in files:
+            a, b = np.load(tmp_path / f"{name}0" / f), np.load(tmp_path / f"{name}1" / f)
+            assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    plain = bench.dump_outputs(str(tmp_path / "plain0"), out, [P], cam)
+    assert plain["rgb"] == [H, W, 3] and plain["alpha"] == [H, W]            # the images whole, the rest sampled
+    assert plain["grad_features_rest"] == [bench.DUMP_ROWS, 15, 3] and plain["loss"] == []
+    rows = np.load(tmp_path / "plain0" / "rows.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "plain0" / "grad_means.npy"), P["means"].grad[rows].numpy())
+
+
 def test_quaternion_multiply_shim_on_cpu_is_pytorch3d_formula():
     """`from pytorch3d.transforms import quaternion_multiply` resolves to the product shim; with CPU operands (the
     reference's bbox optimiser, data/utils/bbox_optimizers.py:155-161) it is pytorch3d's plain-torch formulation: Hamilton
