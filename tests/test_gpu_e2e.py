@@ -127,8 +127,21 @@ def test_metric_size_train_step_runs_and_is_sane():
 def test_tile_culling_does_not_change_results():
     """Exact-exp mode: image, alpha and every gradient source (final T, contributing Gaussian of each pixel)
     are bit-identical with and without the exact tile culling; only the (internal) list positions differ."""
-    from sgn_rast import _lib as L, ops, scenes, step
-    cam, raw = scenes.make_scene("c1")
+    from sgn_rast import scenes
+    _culling_does_not_change_results(*scenes.make_scene("c1"))
+
+
+def test_tile_culling_does_not_change_results_on_stacks():
+    """The same on the adversarial stack family (tests/adversarial_scenes.py): 50-300 splats over single tiles, depth
+    ties, saturation inside the lists — the culling moves every entry's list position relative to the 64-entry batches
+    and the split points of the raster kernels."""
+    import adversarial_scenes as A
+    sc = A.stacks()
+    _culling_does_not_change_results(sc.cam, {k: v.clone() for k, v in sc.raw.items()})
+
+
+def _culling_does_not_change_results(cam, raw):
+    from sgn_rast import _lib as L, ops, step
     P = _to_dev(cam, raw)
     w_img, w_a = step.loss_weights(cam, seed=7, device=DEV)
     L.set_options(exact_exp=1)

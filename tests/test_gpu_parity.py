@@ -4,6 +4,7 @@ tolerance written next to each assert."""
 import pytest
 import torch
 
+from adversarial_scenes import sigma_kernel_order
 from helpers import activated, rel_l2, small_scene
 
 pytestmark = pytest.mark.gpu
@@ -262,8 +263,10 @@ def test_fused_rank_binning_equals_upstream_shaped_path(hip, c_oracle, n, size, 
             py = (t // tb[0]) * 16 + torch.arange(16) + 0.5
             dx = xys[g, 0][:, None, None] - px[None, None, :]
             dy = xys[g, 1][:, None, None] - py[None, :, None]
-            sig = 0.5 * (conics[g, 0][:, None, None] * dx * dx + conics[g, 2][:, None, None] * dy * dy) + \
-                conics[g, 1][:, None, None] * dx * dy
+            # the kernels' own evaluation (fp32, their operation order, single-rounding fmas): near the margin a
+            # differently ordered sum can pass or fail for the wrong reason
+            sig = sigma_kernel_order(conics[g, 0][:, None, None], conics[g, 1][:, None, None],
+                                     conics[g, 2][:, None, None], dx, dy)
             alpha = torch.clamp(opac[g][:, None, None] * torch.exp(-sig), max=0.999)
             assert not bool(((sig >= 0) & (alpha >= 1.0 / 255.0)).any()), "a dropped pair had a valid pixel"
 
