@@ -706,6 +706,19 @@ int sgn_densify_stats(int n, const float *xys_grad /*[n,2]*/, const int32_t *rad
                       float *xys_grad_norm /*[n]*/, float *vis_counts /*[n]*/, float *max_2dsize /*[n]*/,
                       sgn_stream_t stream);
 
+/* Exact k-nearest neighbours of 3-D points (SplatfactoModel.populate_modules, sgn_splatfacto.py:260-264: the reference's
+ * k_nearest_sklearn, :439-457, sklearn NearestNeighbors(k + 1) with the first column dropped).  For every row i of
+ * points [n,3] (finite fp32; non-finite input gives unspecified rows, never an out-of-bounds access): dist[i, :] = the k
+ * smallest |x_i - x_j| over j != i, ascending, as fp32 direct differences; idx[i, :] = those j (distinct, never i; on
+ * equal distances the choice among them is this library's, not sklearn's).  1 <= k <= 16, n > k (else rc < 0).
+ * Deterministic: bit-identical results for the same input.  visited (nullable, device int64): ADDS the number of
+ * candidate distances evaluated (the work bound the tests check).  Asynchronous on `stream`, no host synchronisation;
+ * ws >= sgn_knn_workspace_bytes(n, k), which depends on n and k only (0 when n is out of range).  csrc/knn.hip. */
+size_t sgn_knn_workspace_bytes(int n, int k);
+int sgn_knn(int n, int k, const float *points /*[n,3]*/, float *dist /*[n,k]*/, int32_t *idx /*[n,k]*/,
+            int64_t *visited /*nullable: device int64, += candidate distances evaluated*/, void *ws, size_t ws_bytes,
+            sgn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

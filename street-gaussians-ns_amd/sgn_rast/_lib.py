@@ -110,6 +110,8 @@ SIGNATURES = {
                             _f, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "sgn_raster_bwd_part": (_i, [_i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
                                  _vp, _f, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i, _i]),
+    "sgn_knn_workspace_bytes": (_sz, [_i, _i]),
+    "sgn_knn": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None
