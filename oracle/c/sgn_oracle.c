@@ -701,46 +701,107 @@ static void cube_dir(int face, float u, float v, float out[3]) {
     }
 }
 
+/* The four bilinear taps of one lookup exactly as csrc/cubemap.hip:cube_taps makes them (same fp32 operations): texel
+ * offsets face*R*R + iy*R + ix (-1 = dropped: a corner tap, or every tap of a non-finite direction) and the weights
+ * after the renormalisation that follows a dropped corner tap. */
+static void cube_taps(const float d[3], int R, int off[4], float w[4]) {
+    float u, v;
+    for (int k = 0; k < 4; ++k) { off[k] = -1; w[k] = 0.f; }
+    const int face = cube_face_uv(d, &u, &v);
+    if (face < 0) return;
+    const float fu = u * (float)R - 0.5f, fv = v * (float)R - 0.5f;
+    const float flu = floorf(fu), flv = floorf(fv);
+    const int iu0 = (int)flu, iv0 = (int)flv;
+    const float au = fu - flu, av = fv - flv;
+    float wsum = 0.f;
+    for (int k = 0; k < 4; ++k) {
+        const int iu = iu0 + (k & 1), iv = iv0 + (k >> 1);
+        const float wk = ((k & 1) ? au : 1.f - au) * ((k >> 1) ? av : 1.f - av);
+        const int ou = iu < 0 || iu >= R, ov = iv < 0 || iv >= R;
+        if (ou && ov) continue;                       /* corner tap: dropped, renormalised below */
+        int f = face, ix = iu, iy = iv;
+        if (ou || ov) {                               /* edge tap: re-project the texel centre */
+            float p[3], u2, v2;
+            cube_dir(face, ((float)iu + 0.5f) / (float)R, ((float)iv + 0.5f) / (float)R, p);
+            f = cube_face_uv(p, &u2, &v2);
+            ix = (int)floorf(u2 * (float)R); iy = (int)floorf(v2 * (float)R);
+            ix = ix < 0 ? 0 : (ix > R - 1 ? R - 1 : ix);
+            iy = iy < 0 ? 0 : (iy > R - 1 ? R - 1 : iy);
+        }
+        off[k] = (f * R + iy) * R + ix; w[k] = wk; wsum += wk;
+    }
+    if (wsum > 0.f && wsum < 1.f) {
+        const float inv = 1.f / wsum;
+        for (int k = 0; k < 4; ++k) w[k] *= inv;
+    }
+}
+
+/* dirs [n,3] -> off [n,4] (int), w [n,4]: cube_taps per direction */
+SGO_API void sgo_cube_taps(int n, int R, const float *dirs, int *off, float *w) {
+    for (int i = 0; i < n; ++i) cube_taps(dirs + 3 * (size_t)i, R, off + 4 * (size_t)i, w + 4 * (size_t)i);
+}
+
 /* tex [6,R,R,C], dirs [n,3] -> out [n,C]; if v_out != NULL also accumulates v_tex (zero-filled by the caller) */
 SGO_API void sgo_cube_texture(int n, int R, int C, const float *tex, const float *dirs, float *out,
                               const float *v_out, float *v_tex) {
     for (int i = 0; i < n; ++i) {
-        float u, v;
-        const int face = cube_face_uv(dirs + 3 * i, &u, &v);
-        for (int c = 0; c < C; ++c) out[(size_t)i * C + c] = 0.f;
-        if (face < 0) continue;
-        const float fu = u * (float)R - 0.5f, fv = v * (float)R - 0.5f;
-        const float flu = floorf(fu), flv = floorf(fv);
-        const int iu0 = (int)flu, iv0 = (int)flv;
-        const float au = fu - flu, av = fv - flv;
-        int off[4]; float w[4], wsum = 0.f;
-        for (int k = 0; k < 4; ++k) {
-            const int iu = iu0 + (k & 1), iv = iv0 + (k >> 1);
-            const float wk = ((k & 1) ? au : 1.f - au) * ((k >> 1) ? av : 1.f - av);
-            const int ou = iu < 0 || iu >= R, ov = iv < 0 || iv >= R;
-            off[k] = -1; w[k] = 0.f;
-            if (ou && ov) continue;                       /* corner tap: dropped, renormalised below */
-            int f = face, ix = iu, iy = iv;
-            if (ou || ov) {                               /* edge tap: re-project the texel centre */
-                float p[3], u2, v2;
-                cube_dir(face, ((float)iu + 0.5f) / (float)R, ((float)iv + 0.5f) / (float)R, p);
-                f = cube_face_uv(p, &u2, &v2);
-                ix = (int)floorf(u2 * (float)R); iy = (int)floorf(v2 * (float)R);
-                ix = ix < 0 ? 0 : (ix > R - 1 ? R - 1 : ix);
-                iy = iy < 0 ? 0 : (iy > R - 1 ? R - 1 : iy);
-            }
-            off[k] = (f * R + iy) * R + ix; w[k] = wk; wsum += wk;
-        }
-        const float inv = (wsum > 0.f && wsum < 1.f) ? 1.f / wsum : 1.f;
+        int off[4]; float w[4];
+        cube_taps(dirs + 3 * (size_t)i, R, off, w);
         for (int c = 0; c < C; ++c) {
             double acc = 0.0;
             for (int k = 0; k < 4; ++k) {
                 if (off[k] < 0) continue;
-                acc += (double)(w[k] * inv) * tex[(size_t)off[k] * C + c];
-                if (v_out) v_tex[(size_t)off[k] * C + c] += (w[k] * inv) * v_out[(size_t)i * C + c];
+                acc += (double)w[k] * tex[(size_t)off[k] * C + c];
+                if (v_out) v_tex[(size_t)off[k] * C + c] += w[k] * v_out[(size_t)i * C + c];
             }
             out[(size_t)i * C + c] = (float)acc;
         }
+    }
+}
+
+/* The lookup in the kernels' own order (cube_fwd / sky_fwd / sky_blend_fwd): an fmaf chain over the taps from 0, in
+ * fp32.  With the same directions the kernels' forwards equal this bit for bit. */
+SGO_API void sgo_cube_texture_fwd_f32(int n, int R, int C, const float *tex, const float *dirs, float *out) {
+    for (int i = 0; i < n; ++i) {
+        int off[4]; float w[4];
+        cube_taps(dirs + 3 * (size_t)i, R, off, w);
+        for (int c = 0; c < C; ++c) {
+            float acc = 0.f;
+            for (int k = 0; k < 4; ++k)
+                if (off[k] >= 0) acc = fmaf(w[k], tex[(size_t)off[k] * C + c], acc);
+            out[(size_t)i * C + c] = acc;
+        }
+    }
+}
+
+/* EnvLight's ray directions for an h x w pinhole camera exactly as csrc/cubemap.hip:sky_dir computes them: camera ray
+ * ((px - cx + ju)/fx, (py - cy + jv)/fy, 1) normalised (norm floored at 1e-12), rotated by the row-major c2w (row
+ * stride ld) with an fmaf chain per row, then the GL axis swap (x, z, -y).  jitter [2,h,w] or NULL (pixel centres).
+ * out [h*w, 3]. */
+SGO_API void sgo_sky_dirs(int h, int w, float fx, float fy, float cx, float cy, const float *c2w, int ld,
+                          const float *jitter, float *out) {
+    const int64_t n = (int64_t)h * w;
+    for (int64_t i = 0; i < n; ++i) {
+        const int py = (int)(i / w), px = (int)(i - (int64_t)py * w);
+        const float ju = jitter ? jitter[i] : 0.5f;
+        const float jv = jitter ? jitter[n + i] : 0.5f;
+        const float dx = ((float)px - cx + ju) / fx, dy = ((float)py - cy + jv) / fy;
+        const float nrm = fmaxf(sqrtf(fmaf(dx, dx, fmaf(dy, dy, 1.f))), 1e-12f);
+        const float x = dx / nrm, y = dy / nrm, z = 1.f / nrm;
+        const float *M = c2w;
+        const float wx = fmaf(M[2], z, fmaf(M[1], y, M[0] * x));
+        const float wy = fmaf(M[ld + 2], z, fmaf(M[ld + 1], y, M[ld] * x));
+        const float wz = fmaf(M[2 * ld + 2], z, fmaf(M[2 * ld + 1], y, M[2 * ld] * x));
+        out[3 * i] = wx; out[3 * i + 1] = wz; out[3 * i + 2] = -wy;
+    }
+}
+
+/* sky_blend_fwd's composite in its order: min(rgb, 1) * a + sky * (1 - a), two products and a sum, no contraction.
+ * sky [n,3] (the fp32 lookup), rgb [n,3], alpha [n] -> out [n,3] */
+SGO_API void sgo_sky_blend_f32(int64_t n, const float *sky, const float *rgb, const float *alpha, float *out) {
+    for (int64_t i = 0; i < n; ++i) {
+        const float a = alpha[i];
+        for (int c = 0; c < 3; ++c) out[3 * i + c] = fminf(rgb[3 * i + c], 1.f) * a + sky[3 * i + c] * (1.f - a);
     }
 }
 

@@ -232,6 +232,48 @@ def cube_texture(tex, dirs, v_out=None):
     return (out, v_tex) if v_out is not None else out
 
 
+def cube_taps(dirs, R):
+    """dirs [n,3] -> (off [n,4] int32, w [n,4] fp32): the kernels' four bilinear taps per lookup
+    (cubemap.hip:cube_taps), texel offsets face*R*R + iy*R + ix with -1 for a dropped tap, weights after the corner renormalisation."""
+    d = _f(dirs).reshape(-1, 3).contiguous()
+    n = d.shape[0]
+    off = torch.empty(n, 4, dtype=torch.int32)
+    w = torch.empty(n, 4)
+    lib().sgo_cube_taps(C.c_int(n), C.c_int(R), _p(d), _p(off), _p(w))
+    return off, w
+
+
+def cube_texture_f32(tex, dirs):
+    """The lookup in the kernels' order (fp32 fmaf chain over the taps): tex [6,R,R,C], dirs [n,3] -> out [n,C]."""
+    tex, d = _f(tex), _f(dirs).reshape(-1, 3).contiguous()
+    n, R, Cc = d.shape[0], tex.shape[1], tex.shape[3]
+    out = torch.empty(n, Cc)
+    lib().sgo_cube_texture_fwd_f32(C.c_int(n), C.c_int(R), C.c_int(Cc), _p(tex), _p(d), _p(out))
+    return out
+
+
+def sky_dirs(h, w, fx, fy, cx, cy, c2w, jitter=None):
+    """[h*w, 3] GL-axis ray directions exactly as the fused sky kernels compute them (cubemap.hip:sky_dir); ``c2w`` is
+    [3,>=3] row-major (any row stride), ``jitter`` [2,h,w] or None (pixel centres)."""
+    m = c2w.detach().to(torch.float32)
+    if m.stride(-1) != 1:
+        m = m.contiguous()
+    out = torch.empty(h * w, 3)
+    jit = None if jitter is None else _f(jitter).reshape(2, h, w).contiguous()
+    lib().sgo_sky_dirs(C.c_int(h), C.c_int(w), C.c_float(fx), C.c_float(fy), C.c_float(cx), C.c_float(cy),
+                       C.c_void_p(m.data_ptr()), C.c_int(m.stride(0)), _p(jit) if jit is not None else None, _p(out))
+    return out
+
+
+def sky_blend_f32(sky, rgb, alpha):
+    """sky_blend's composite in the kernel's order: min(rgb,1)*a + sky*(1-a) in fp32 without contraction; sky and rgb
+    [n,3], alpha [n] -> [n,3]."""
+    s, r, a = _f(sky).reshape(-1, 3), _f(rgb).reshape(-1, 3), _f(alpha).reshape(-1)
+    out = torch.empty(s.shape[0], 3)
+    lib().sgo_sky_blend_f32(C.c_int64(s.shape[0]), _p(s), _p(r), _p(a), _p(out))
+    return out
+
+
 def l1_ssim(x, y, data_range: float = 1.0):
     """(mean |y - x|, mean SSIM) of two [H,W,3] images, double precision inside."""
     x, y = _f(x), _f(y)
