@@ -194,6 +194,26 @@ int sgn_project_bwd_fused(int n, const float *means_local, const float *log_scal
                           const float *v_compensation, float *v_means_local, float *v_log_scales,
                           float *v_quats_raw, int semantics, int img_h, int img_w, sgn_stream_t stream);
 
+/* sgn_project_bwd_fused plus the gradient w.r.t. the pose table: v_poses [m,16] = dL/dR (9, row-major) | dL/dt (3) |
+ * dL/dq_o2w (4), summed over the rows of each object with radii > 0 (culled rows contribute nothing; an object without
+ * rows gets exact zeros; row 0, the background, is computed like the others).  The per-Gaussian outputs are
+ * bit-identical to sgn_project_bwd_fused's.  Precondition: object_ids is non-decreasing, and object o owns rows
+ * [object_offsets[o], object_offsets[o+1]) (device int32 [m+1], 0 <= offsets <= n) — the layout of
+ * sgn_rast.fused.object_ids_for.  Deterministic (per-wave partials in `ws`, then fixed-order sums per object in two
+ * small passes; no float atomics).  ws: 16-byte aligned, ws_bytes >= sgn_project_pose_workspace_bytes(n, m) (0 when n < 1 or m < 1).
+ * Return codes beyond sgn_project_bwd_fused's: -8 m < 1; -9 object_offsets or v_poses NULL; -10 ws NULL, misaligned
+ * or smaller than the workspace size; -11 object_ids and poses both NULL (no pose to differentiate). */
+size_t sgn_project_pose_workspace_bytes(int n, int m);
+int sgn_project_bwd_fused_pose(int n, const float *means_local, const float *log_scales, float glob_scale,
+                               const float *quats_raw, const int32_t *object_ids, const float *poses,
+                               const float *viewmat12, float fx, float fy, const float *cov3d,
+                               const int32_t *radii, const float *conics, const float *compensation,
+                               const float *v_xy, const float *v_depth, const float *v_conic,
+                               const float *v_compensation, float *v_means_local, float *v_log_scales,
+                               float *v_quats_raw, int semantics, int img_h, int img_w, int m,
+                               const int32_t *object_offsets /*device [m+1]*/, float *v_poses /*[m,16]*/, void *ws,
+                               size_t ws_bytes, sgn_stream_t stream);
+
 /* Backward of the DROP-IN call `project_gaussians(means, scales, g, X / X.norm(dim=-1, keepdim=True))`
  * (sgn_splatfacto.py:857-873) taken one step further back than sgn_project_bwd: gradients w.r.t. the means, the
  * LOGARITHM of the scales (v_scale * scale — `scales` arrives activated, as the caller computed it, no second exp) and

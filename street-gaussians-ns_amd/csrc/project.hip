@@ -209,7 +209,16 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
     num_tiles_hit[i] = o_n;
 }
 
-template <int FUSED>
+// Pose gradient of the fused front end (POSE = true): per-wave partial sums of the 16 pose-table terms, one slot per
+// (wave w, object o) pair that has rows in the wave, at slot w + o of `part` [n_waves + m, 16].  With object rows
+// contiguous and ids non-decreasing, w + o strictly increases from one such pair to the next along the rows, so
+// slots are unique and every pair's slot is written exactly once (by the last lane of its segment).
+struct PosePart {
+    float *part;   // nullptr unless POSE
+    int m;         // rows of the pose table: ids outside [0, m) write nothing
+};
+
+template <int FUSED, bool POSE = false>
 __global__ __launch_bounds__(256) void project_bwd_kernel(
     int n, const float *__restrict__ means, const float *__restrict__ scales,
     const float *__restrict__ quats, Cam cam, Fuse fuse, const float *__restrict__ cov3d,
@@ -217,9 +226,16 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
     const float *__restrict__ comp, const float *__restrict__ v_xy,
     const float *__restrict__ v_depth, const float *__restrict__ v_conic,
     const float *__restrict__ v_comp, float *__restrict__ v_cov2d, float *__restrict__ v_cov3d,
-    float *__restrict__ v_mean, float *__restrict__ v_scale, float *__restrict__ v_quat) {
+    float *__restrict__ v_mean, float *__restrict__ v_scale, float *__restrict__ v_quat, PosePart pp = {nullptr, 0}) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
+    if constexpr (!POSE) {
+        if (i >= n) return;
+    }
+    // pose terms of this row: dL/dR (9, row-major) | dL/dt (3) | dL/dq_o2w (4); zero for culled rows and lanes past n
+    float pv[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) pv[k] = 0.f;
+    if (!POSE || i < n) {
     float o_vm[3] = {0.f, 0.f, 0.f}, o_vs[3] = {0.f, 0.f, 0.f}, o_vq[4] = {0.f, 0.f, 0.f, 0.f};
     float o_vc2[3] = {0.f, 0.f, 0.f}, o_vc3[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (radii[i] > 0) {
@@ -366,6 +382,20 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
                 o_vm[0] = P[0] * v0 + P[3] * v1 + P[6] * v2;
                 o_vm[1] = P[1] * v0 + P[4] * v1 + P[7] * v2;
                 o_vm[2] = P[2] * v0 + P[5] * v1 + P[8] * v2;
+                if constexpr (POSE) {
+                    // means_w = R m + t: dL/dR = v_w m^T, dL/dt = v_w.  q_w = a (x) b with a = q_o2w, b = q_raw:
+                    // dL/da = M_R(b)^T g, M_R(b) the matrix of right multiplication by b
+                    const float m0 = means[3 * i], m1 = means[3 * i + 1], m2 = means[3 * i + 2];
+                    pv[0] = v0 * m0; pv[1] = v0 * m1; pv[2] = v0 * m2;
+                    pv[3] = v1 * m0; pv[4] = v1 * m1; pv[5] = v1 * m2;
+                    pv[6] = v2 * m0; pv[7] = v2 * m1; pv[8] = v2 * m2;
+                    pv[9] = v0; pv[10] = v1; pv[11] = v2;
+                    const float bw = quats[4 * i], bx = quats[4 * i + 1], by = quats[4 * i + 2], bz = quats[4 * i + 3];
+                    pv[12] = bw * g[0] + bx * g[1] + by * g[2] + bz * g[3];
+                    pv[13] = -bx * g[0] + bw * g[1] - bz * g[2] + by * g[3];
+                    pv[14] = -by * g[0] + bz * g[1] + bw * g[2] - bx * g[3];
+                    pv[15] = -bz * g[0] - by * g[1] + bx * g[2] + bw * g[3];
+                }
             } else {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) o_vq[k] = g[k];
@@ -382,8 +412,109 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
     if (v_cov3d != nullptr)
 #pragma unroll
         for (int k = 0; k < 6; ++k) v_cov3d[6 * i + k] = o_vc3[k];
+    }
+    if constexpr (POSE) {
+        // segmented inclusive scan over the wave, keyed by object id (ids non-decreasing: equal ids d lanes apart
+        // bracket one segment).  Fixed shuffle tree: the same bits on every run.  Lanes past n form a segment of
+        // their own that stores nothing.
+        const int lane = threadIdx.x & 63;
+        const int oid = i < n ? fuse.object_ids[i] : 0x7fffffff;
+#pragma unroll
+        // (every shuffle runs on all 64 lanes: a bpermute reading a lane that is switched off gets 0, not its id)
+        for (int d = 1; d < 64; d <<= 1) {
+            const int up = __shfl_up(oid, d);
+            const bool take = lane >= d && up == oid;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const float u = __shfl_up(pv[k], d);
+                if (take) pv[k] = u + pv[k];
+            }
+        }
+        const int down = __shfl_down(oid, 1);
+        const bool last = lane == 63 || down != oid;
+        if (last && i < n && oid >= 0 && oid < pp.m) {
+            float4 *dst = reinterpret_cast<float4 *>(pp.part + 16 * ((size_t)(i >> 6) + (size_t)oid));
+#pragma unroll
+            for (int k = 0; k < 4; ++k) dst[k] = make_float4(pv[4 * k], pv[4 * k + 1], pv[4 * k + 2], pv[4 * k + 3]);
+        }
+    }
 }
 
+// Per-object sums of the wave partials, in two passes with a fixed order (no float atomics):
+// pose_sum_kernel, grid (m, POSE_BLOCKS): block (o, b) takes the b-th of POSE_BLOCKS contiguous ranges of object o's
+// waves (slots w + o); 16 streams x 16 columns per block; a stream sums its contiguous run in groups of 8 independent
+// loads (3-level tree) fed to a binary-counter cascade (depth <= floor(log2 groups) + 1), then the 16 streams meet in a
+// 4-level LDS tree; the block's sum goes to `mid` [m, POSE_BLOCKS, 16].  pose_final_kernel: one block per object
+// sums its POSE_BLOCKS values, 4 per stream (2 levels) then a 4-level LDS tree.  Depth of the whole sum per element:
+// 6 (wave scan) + 3 + floor(log2 groups) + 1 + 4 + 6 <= log2(n_o) + 4.  An object without rows gets exact zeros.
+// Offsets are clamped to [0, n], so malformed offsets never read outside `part`.
+constexpr int POSE_BLOCKS = 64;
+constexpr int POSE_CASCADE = 24;
+__device__ __forceinline__ float pose_stream_reduce(float *red, float v) {
+    const int t = threadIdx.x, s = t >> 4;
+    red[t] = v;
+    __syncthreads();
+#pragma unroll
+    for (int h = 8; h >= 1; h >>= 1) {
+        if (s < h) red[t] = red[t] + red[t + 16 * h];
+        __syncthreads();
+    }
+    return red[t & 15];
+}
+
+__global__ __launch_bounds__(256) void pose_sum_kernel(int n, const int32_t *__restrict__ offsets,
+                                                       const float *__restrict__ part, float *__restrict__ mid) {
+    __shared__ float red[256];
+    const int o = blockIdx.x, blk = blockIdx.y, t = threadIdx.x, c = t & 15, s = t >> 4;
+    const int lo = min(max(offsets[o], 0), n), hi = min(max(offsets[o + 1], lo), n);
+    float total = 0.f;
+    if (hi > lo) {
+        const int w0 = lo >> 6, W = ((hi - 1) >> 6) - w0 + 1;
+        const int per_blk = (W + POSE_BLOCKS - 1) / POSE_BLOCKS;
+        const int bl = min(W, blk * per_blk), bh = min(W, bl + per_blk);
+        const int run = (bh - bl + 15) / 16;
+        const int a = min(bh, bl + s * run), b = min(bh, a + run);
+        const float *src = part + 16 * ((size_t)w0 + (size_t)o) + c;
+        float acc[POSE_CASCADE];
+#pragma unroll
+        for (int l = 0; l < POSE_CASCADE; ++l) acc[l] = 0.f;
+        int groups = 0;
+        for (int j = a; j < b; j += 8, ++groups) {
+            float x[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) x[k] = j + k < b ? src[16 * (size_t)(j + k)] : 0.f;
+            float v = ((x[0] + x[1]) + (x[2] + x[3])) + ((x[4] + x[5]) + (x[6] + x[7]));
+#pragma unroll
+            for (int l = 0; l < POSE_CASCADE; ++l) {
+                if ((groups >> l) & 1) {
+                    v = acc[l] + v;
+                } else {
+                    acc[l] = v;
+                    break;
+                }
+            }
+        }
+        bool first = true;
+#pragma unroll
+        for (int l = 0; l < POSE_CASCADE; ++l)
+            if ((groups >> l) & 1) {
+                total = first ? acc[l] : acc[l] + total;
+                first = false;
+            }
+    }
+    const float r = pose_stream_reduce(red, total);
+    if (s == 0) mid[16 * ((size_t)o * POSE_BLOCKS + blk) + c] = r;
+}
+
+__global__ __launch_bounds__(256) void pose_final_kernel(const float *__restrict__ mid, float *__restrict__ v_poses) {
+    static_assert(POSE_BLOCKS == 64, "4 values per stream x 16 streams");
+    __shared__ float red[256];
+    const int o = blockIdx.x, t = threadIdx.x, c = t & 15, s = t >> 4;
+    const float *src = mid + 16 * ((size_t)o * POSE_BLOCKS + 4 * s) + c;
+    const float v = (src[0] + src[16]) + (src[32] + src[48]);
+    const float r = pose_stream_reduce(red, v);
+    if (s == 0) v_poses[16 * o + c] = r;
+}
 Cam make_cam(const float *V, float fx, float fy, float cx, float cy, int h, int w, int block,
              float clip, float glob_scale, int semantics = 0) {
     Cam c;
@@ -509,6 +640,53 @@ SGN_EXPORT int sgn_project_bwd_fused(int n, const float *means_local, const floa
                        means_local, log_scales, quats_raw, cam, Fuse{object_ids, poses}, cov3d, radii, conics,
                        compensation, v_xy, v_depth, v_conic, v_compensation, nullptr, nullptr, v_means_local,
                        v_log_scales, v_quats_raw);
+    sgn_timing_end(SGN_T_PROJECT_BWD, stream);
+    SGN_LAUNCH_CHECK();
+    return 0;
+}
+
+// Pose gradient riding the fused backward: same per-Gaussian outputs as sgn_project_bwd_fused (same code, POSE adds the
+// per-wave partials after the stores), then one small pass sums the partials per object.  ws: the partials,
+// [ceil(n/64) + m, 16] floats.
+SGN_EXPORT size_t sgn_project_pose_workspace_bytes(int n, int m) {
+    if (n < 1 || m < 1) return 0;
+    return ((size_t)sgn_cdiv(n, 64) + (size_t)m + (size_t)m * POSE_BLOCKS) * 16 * sizeof(float);
+}
+
+SGN_EXPORT int sgn_project_bwd_fused_pose(int n, const float *means_local, const float *log_scales, float glob_scale,
+                                          const float *quats_raw, const int32_t *object_ids, const float *poses,
+                                          const float *viewmat12, float fx, float fy, const float *cov3d,
+                                          const int32_t *radii, const float *conics, const float *compensation,
+                                          const float *v_xy, const float *v_depth, const float *v_conic,
+                                          const float *v_compensation, float *v_means_local, float *v_log_scales,
+                                          float *v_quats_raw, int semantics, int img_h, int img_w, int m,
+                                          const int32_t *object_offsets, float *v_poses, void *ws, size_t ws_bytes,
+                                          sgn_stream_t stream) {
+    SGN_ARG_CHECK(n >= 0, -1);
+    SGN_ARG_CHECK(m >= 1, -8);
+    SGN_ARG_CHECK(object_offsets != nullptr && v_poses != nullptr, -9);
+    SGN_ARG_CHECK(object_ids != nullptr || poses != nullptr, -11);
+    SGN_ARG_CHECK((object_ids == nullptr) == (poses == nullptr), -6);
+    hipStream_t s = (hipStream_t)stream;
+    if (n == 0) {
+        SGN_HIP_CHECK(hipMemsetAsync(v_poses, 0, (size_t)m * 16 * sizeof(float), s));
+        return 0;
+    }
+    SGN_ARG_CHECK(means_local && log_scales && quats_raw && viewmat12 && cov3d && radii && conics && v_xy &&
+                      v_conic && v_means_local && v_log_scales && v_quats_raw, -4);
+    SGN_ARG_CHECK(v_compensation == nullptr || compensation != nullptr, -5);
+    SGN_ARG_CHECK(!(semantics & SGN_SEM_EWA_VJP_CLAMPED) || (img_h > 0 && img_w > 0), -7);
+    SGN_ARG_CHECK(ws != nullptr && (reinterpret_cast<uintptr_t>(ws) & 15) == 0 &&
+                      ws_bytes >= sgn_project_pose_workspace_bytes(n, m), -10);
+    const Cam cam = bwd_cam(viewmat12, fx, fy, glob_scale, semantics, img_h, img_w);
+    float *part = static_cast<float *>(ws), *mid = part + 16 * ((size_t)sgn_cdiv(n, 64) + (size_t)m);
+    sgn_timing_begin(SGN_T_PROJECT_BWD, stream);
+    hipLaunchKernelGGL((project_bwd_kernel<1, true>), dim3(sgn_cdiv(n, 256)), dim3(256), 0, s, n, means_local,
+                       log_scales, quats_raw, cam, Fuse{object_ids, poses}, cov3d, radii, conics, compensation, v_xy,
+                       v_depth, v_conic, v_compensation, nullptr, nullptr, v_means_local, v_log_scales, v_quats_raw,
+                       PosePart{part, m});
+    hipLaunchKernelGGL(pose_sum_kernel, dim3(m, POSE_BLOCKS), dim3(256), 0, s, n, object_offsets, part, mid);
+    hipLaunchKernelGGL(pose_final_kernel, dim3(m), dim3(256), 0, s, mid, v_poses);
     sgn_timing_end(SGN_T_PROJECT_BWD, stream);
     SGN_LAUNCH_CHECK();
     return 0;

@@ -61,9 +61,32 @@ def object_ids_for(counts, device) -> torch.Tensor:
     if key not in _LAYOUTS:
         if len(_LAYOUTS) > 64:
             _LAYOUTS.clear()
-        _LAYOUTS[key] = torch.repeat_interleave(torch.arange(len(counts), dtype=torch.int32),
-                                                torch.tensor([int(c) for c in counts])).to(device)
+        ids = torch.repeat_interleave(torch.arange(len(counts), dtype=torch.int32),
+                                      torch.tensor([int(c) for c in counts])).to(device)
+        # the segment offsets [M+1] of the same layout, for the pose gradient (sgn_project_bwd_fused_pose)
+        offs = torch.zeros(len(counts) + 1, dtype=torch.int32)
+        offs[1:] = torch.cumsum(torch.tensor([int(c) for c in counts], dtype=torch.int64), 0).to(torch.int32)
+        ids._sgn_offsets = offs.to(device)
+        _LAYOUTS[key] = ids
     return _LAYOUTS[key]
+
+
+def object_offsets(object_ids: torch.Tensor, m: int) -> torch.Tensor:
+    """int32 [m+1] device offsets: object o owns rows ``[off[o], off[o+1])``.  Free for ids that :func:`object_ids_for`
+    built (cached with the layout); for any other ids, derived and validated with torch at the cost of ONE host sync,
+    raising ``ValueError`` unless the ids are non-decreasing and lie in ``[0, m)``."""
+    offs = getattr(object_ids, "_sgn_offsets", None)
+    if offs is not None and offs.numel() == m + 1:
+        return offs
+    ids = object_ids.detach().to(torch.int64).reshape(-1)
+    if ids.numel() == 0:
+        return torch.zeros(m + 1, dtype=torch.int32, device=object_ids.device)
+    bad = (ids[1:] < ids[:-1]).any() | (ids[0] < 0) | (ids[-1] >= m)
+    if bool(bad):                                   # the one sync
+        raise ValueError("object_ids must be non-decreasing and in [0, m) for a pose gradient "
+                         "(background first, then each object's rows; fused.object_ids_for builds that layout)")
+    counts = torch.bincount(ids, minlength=m)
+    return torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)]).to(torch.int32)
 
 
 def cat_features_dc(parts) -> torch.Tensor:
@@ -130,7 +153,7 @@ def scene_graph_tables(counts, object_poses, object_idft, device) -> dict:
 class _ProjectFused(Function):
     @staticmethod
     def forward(ctx, means, log_scales, quats_raw, object_ids, poses, viewmat, fx, fy, cx, cy, img_height,
-                img_width, block_width, clip_thresh, glob_scale):
+                img_width, block_width, clip_thresh, glob_scale, offsets=None):
         dev = L.require_device(means, log_scales, quats_raw, viewmat, object_ids, poses)
         n = means.shape[0]
         if n < 1 or means.shape[-1] != 3:
@@ -156,6 +179,9 @@ class _ProjectFused(Function):
         saved = [means_c, ls_c, q_c, vm, cov3d, radii, conics, comp]
         if ctx.has_obj:
             saved += [oid, pos]
+        ctx.pose_grad = offsets is not None
+        if ctx.pose_grad:
+            saved.append(offsets)
         ctx.save_for_backward(*saved)
         ctx.mark_non_differentiable(radii, nth)
         ctx.set_materialize_grads(False)     # unused outputs arrive as None (ops._project_forward has the note)
@@ -176,12 +202,24 @@ class _ProjectFused(Function):
         al = getattr(ctx, "arena_leaves", None)       # (the DP bucket's slices, ops._grad_arena)
         v_m, v_s, v_q = (_ops._leaf_grad(al, 0, (n, 3), f32), _ops._leaf_grad(al, 1, (n, 3), f32),
                          _ops._leaf_grad(al, 2, (n, 4), f32))
+        if ctx.pose_grad and ctx.needs_input_grad[4]:
+            # the same backward plus the per-object sums of the pose-table gradient (csrc/project.hip, POSE)
+            m = pos.shape[0]
+            lib = L.load()
+            ws = torch.empty(max(1, lib.sgn_project_pose_workspace_bytes(n, m)), dtype=torch.uint8, device=dev)
+            v_pos = torch.empty(m, 16, **f32)
+            L.check(lib.sgn_project_bwd_fused_pose(
+                n, L.ptr(means), L.ptr(ls), gs, L.ptr(q), L.ptr(oid), L.ptr(pos), L.ptr(vm), fx, fy, L.ptr(cov3d),
+                L.ptr(radii), L.ptr(conics), L.ptr(comp), L.ptr(v_xys), L.ptr(v_depths), L.ptr(v_conics),
+                L.ptr(v_comp), L.ptr(v_m), L.ptr(v_s), L.ptr(v_q), ctx.sem, ctx.img_hw[0], ctx.img_hw[1], m,
+                L.ptr(saved[10]), L.ptr(v_pos), L.ptr(ws), ws.numel(), L.stream_ptr()), "sgn_project_bwd_fused_pose")
+            return (v_m, v_s, v_q, None, v_pos) + (None,) * 11
         L.check(L.load().sgn_project_bwd_fused(
             n, L.ptr(means), L.ptr(ls), gs, L.ptr(q), L.ptr(oid), L.ptr(pos), L.ptr(vm), fx, fy, L.ptr(cov3d),
             L.ptr(radii), L.ptr(conics), L.ptr(comp), L.ptr(v_xys), L.ptr(v_depths), L.ptr(v_conics), L.ptr(v_comp),
             L.ptr(v_m), L.ptr(v_s), L.ptr(v_q), ctx.sem, ctx.img_hw[0], ctx.img_hw[1], L.stream_ptr()),
             "sgn_project_bwd_fused")
-        return (v_m, v_s, v_q) + (None,) * 12
+        return (v_m, v_s, v_q) + (None,) * 13
 
 
 def project_gaussians_fused(means, log_scales, quats_raw, viewmat, fx, fy, cx, cy, img_height, img_width,
@@ -189,12 +227,17 @@ def project_gaussians_fused(means, log_scales, quats_raw, viewmat, fx, fy, cx, c
                             poses: Optional[torch.Tensor] = None, clip_thresh: float = 0.01,
                             glob_scale: float = 1.0):
     """``project_gaussians(R_o m + t_o, exp(log_scales), glob_scale, normalize(q_o2w (x) q_raw), ...)`` in one
-    kernel; gradients w.r.t. the local means, log-scales and raw quaternions.  Same 7-tuple as upstream."""
+    kernel; gradients w.r.t. the local means, log-scales and raw quaternions, and — when ``poses.requires_grad`` —
+    w.r.t. the pose table [M,16] (summed per object in the same backward kernel; needs each object's rows contiguous,
+    see :func:`object_offsets`).  Same 7-tuple as upstream."""
     assert block_width > 1 and block_width <= 16, "block_width must be between 2 and 16"
     assert (object_ids is None) == (poses is None), "object_ids and poses go together"
+    offsets = None
+    if poses is not None and poses.requires_grad and torch.is_grad_enabled():
+        offsets = object_offsets(object_ids, int(poses.shape[0]))
     return _ProjectFused.apply(means.contiguous(), log_scales.contiguous(), quats_raw.contiguous(), object_ids, poses,
                                viewmat.contiguous(), fx, fy, cx, cy, img_height, img_width, block_width, clip_thresh,
-                               glob_scale)
+                               glob_scale, offsets)
 
 
 # hook for sgn_rast.dp.SHGradExchange (see ops._sh_exchange): `claims_leaves` at forward time, `tap_fused` (means,
@@ -321,7 +364,8 @@ def spherical_harmonics_fused(degrees_to_use: int, means, cam_pos, features_dc, 
     ``dc_eff = sum_f features_dc[:, f] * idft[object, f]`` — view directions, Fourier DC, concat, SH and
     the colour post-processing in one pass; with ``poses`` the means are LOCAL and moved to the world frame
     in-kernel (no gradient to ``means``, as in the reference: ``.detach()``
-    at sgn_splatfacto.py:934)."""
+    at sgn_splatfacto.py:934).  For the same reason no gradient reaches ``poses`` from here: the view directions are
+    built from detached means, so only the projection carries the pose gradient."""
     if isinstance(features_dc, (list, tuple)):
         # un-concatenated sub-models (round 4): one features_dc [n_p, F_p, 3] / features_rest [n_p, K-1, 3] pair per
         # sub-model in aggregated order; part p uses pose row p and idft row p (`fused.scene_graph_tables`); no torch.cat
