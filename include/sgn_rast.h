@@ -739,6 +739,77 @@ int sgn_knn(int n, int k, const float *points /*[n,3]*/, float *dist /*[n,k]*/, 
             int64_t *visited /*nullable: device int64, += candidate distances evaluated*/, void *ws, size_t ws_bytes,
             sgn_stream_t stream);
 
+/* BATCHED VIEWS (no upstream counterpart; gsplat 1.x takes [C] cameras per call).  B = n_views cameras share one image
+ * size (img_h, img_w), 16x16 tiles and one set of N Gaussians in the fused front end's raw form (means, log-scales, raw
+ * quaternions, opacity logits, features_dc [N,1,3], features_rest [N,k-1,3]; no scene graph).  Row b*N + i of every
+ * per-row array is Gaussian i seen from camera b; images are [B,H,W,C].  Every output of view b is bit-identical to the
+ * single-view fused path for camera b alone (same kernel bodies, local pixel coordinates); gradients w.r.t. the N
+ * Gaussians are sums over the views, summed in registers in ascending view order (projection, SH, opacity: no float
+ * atomics) — the raster backward keeps its atomics.
+ * `cams`: HOST array of n_views rows; it is copied into the kernel arguments (no device buffer).
+ * Return codes of every entry below: -1 n_views outside [1, SGN_VIEWS_MAX]; -2 n < 0 or n_views * n >= 2^28 (sorted ids
+ * carry quadrant masks in bits 28-31); -3 bad image size / block width (the raster entries need block_width 16); -4 a
+ * required pointer is NULL; -5 workspace / arena too small; -6 isect_capacity < 1 or >= 2^31; SGN_E_CAPACITY as
+ * sgn_rasterize_fwd_all. */
+#define SGN_VIEWS_MAX 16
+typedef struct sgn_view_cam {
+    float viewmat[12];  /* world -> camera, 3x4 row-major */
+    float fx, fy, cx, cy;
+    float cam_pos[3];   /* camera centre in world coordinates (SH view directions) */
+} sgn_view_cam;
+
+/* Projection: outputs [n_views * n, ...] as sgn_project_fwd_fused per camera (no object ids / poses). */
+int sgn_project_views_fwd(int n_views, int n, const sgn_view_cam *cams, const float *means, const float *log_scales,
+                          float glob_scale, const float *quats_raw, int img_h, int img_w, int block_width,
+                          float clip_thresh, float *cov3d, float *xys, float *depths, int32_t *radii, float *conics,
+                          float *compensation, int32_t *num_tiles_hit, int semantics, sgn_stream_t stream);
+/* Its backward: v_* [n_views * n, ...] in, gradients w.r.t. the n Gaussians out (summed over the views). */
+int sgn_project_views_bwd(int n_views, int n, const sgn_view_cam *cams, const float *means, const float *log_scales,
+                          float glob_scale, const float *quats_raw, const float *cov3d, const int32_t *radii,
+                          const float *conics, const float *compensation, const float *v_xy, const float *v_depth,
+                          const float *v_conic, const float *v_compensation, float *v_means, float *v_log_scales,
+                          float *v_quats_raw, int semantics, int img_h, int img_w, sgn_stream_t stream);
+
+/* SH colours of every view, clamp(SH + 0.5, min 0) (post_half_clamp) as sgn_sh_fwd_fused with n_fourier = 1: the
+ * coefficients are read once, colors [n_views * n, 3].  The backward sums the views' coefficient gradients. */
+int sgn_sh_views_fwd(int n_views, int n, int k, int degree, const sgn_view_cam *cams, const float *means,
+                     const float *features_dc, const float *features_rest, int post_half_clamp, float *colors,
+                     sgn_stream_t stream);
+int sgn_sh_views_bwd(int n_views, int n, int k, int degree, const sgn_view_cam *cams, const float *means,
+                     int post_half_clamp, const float *colors, const float *v_colors, float *v_features_dc,
+                     float *v_features_rest, sgn_stream_t stream);
+
+/* The forward of the batched rasterization in ONE call, as sgn_rasterize_fwd_all over all views: the depth ranking of
+ * all n_views * n rows, the per-row tile counts on each view's own grid, ONE host wait for the intersection count, the
+ * rows, the emission with tile id = view * tiles_per_view + local tile (each tile's list then holds its own view's rows
+ * in depth order), the tile sort, the launch order over all tiles and the forward kernels.  opacity_logits [n] (row
+ * b*n+i reads entry i); out_img [B,H,W,3], final_Ts / final_idx / out_depth (NULL: no depth channel) [B,H,W];
+ * tile_bins and tile_stats [B*tiles, 2] (tile_stats right behind tile_bins saves a clear), tile_order [B*tiles + 2],
+ * rows: sgn_raster_workspace_bytes(n_views * n).  Returns 0 with *n_isect_host = 0 when nothing is visible (the
+ * images are not written). */
+size_t sgn_rasterize_views_arena_bytes(int n_views, int n, int64_t isect_capacity);
+int sgn_rasterize_views_fwd_all(int n_views, int n, const float *xys, const float *depths, const int32_t *radii,
+                                const float *conics, const float *colors, const float *opacity_logits, int cull,
+                                int img_h, int img_w, int block_width, const float *background3, int quadrant_masks,
+                                float *out_img, float *final_Ts, int32_t *final_idx, float *out_depth,
+                                int32_t *gaussian_ids_sorted, int64_t isect_capacity, int32_t *tile_bins,
+                                int32_t *tile_order, int32_t *tile_stats, void *rows, size_t rows_bytes,
+                                void *order_scratch, size_t order_scratch_bytes, void *arena, size_t arena_bytes,
+                                int32_t *count_pinned, int64_t *n_isect_host, int sort_rank_mode, int semantics,
+                                const sgn_raster_opts *opts, sgn_stream_t stream);
+/* Its backward: launch order from the forward's tile statistics, the reverse walks of every view's tiles (gradient
+ * atomics into grad_ws, sgn_raster_bwd_workspace_bytes(n_views * n)), then one pass that unpacks v_xy / v_conic /
+ * v_colors [n_views * n, ...] and sums d/d logit over the views into v_opacity_logits [n]. */
+int sgn_rasterize_views_bwd_all(int n_views, int n, int64_t n_isect, int img_h, int img_w,
+                                const int32_t *gaussian_ids_sorted, const int32_t *tile_bins, const int32_t *tile_stats,
+                                const float *conics, const float *opacity_logits, const float *background3,
+                                const float *final_Ts, const int32_t *final_idx, const float *v_out_img,
+                                const float *v_out_alpha, float alpha_clamp_bwd, float *v_xy, float *v_conic,
+                                float *v_colors, float *v_opacity_logits, const void *rows, size_t rows_bytes,
+                                void *grad_ws, size_t grad_ws_bytes, int32_t *tile_order, void *order_scratch,
+                                size_t order_scratch_bytes, int small_q16, const sgn_raster_opts *opts,
+                                sgn_stream_t stream, sgn_stream_t aux_stream);
+
 #ifdef __cplusplus
 }
 #endif

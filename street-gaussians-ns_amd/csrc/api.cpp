@@ -288,6 +288,23 @@ int sgn_raster_fwd_precleared(int img_h, int img_w, int block_width, int n, int6
                               int32_t *tile_kmax, const float *depths, float *out_depth, const sgn_raster_opts *opts,
                               sgn_stream_t stream);   // raster.hip
 
+int sgn_bin_intersect_views(int n_views, int n, int64_t n_isect, const float *bin_records, const int32_t *cum_by_rank,
+                            const int32_t *gid_by_rank, int tiles_x, int tiles_y, int32_t *gaussian_ids_sorted,
+                            int32_t *tile_bins, int quadrant_masks, void *ws, size_t ws_bytes,
+                            const int32_t *n_isect_dev, int sort_rank_mode, int also_zero_words,
+                            sgn_stream_t stream);                                          // binning.hip
+int sgn_views_repeat(int n, int n_views, const float *src, float *dst, sgn_stream_t stream);   // raster.hip
+int sgn_raster_views_fwd(int n_views, int img_h, int img_w, const int32_t *ids, const int32_t *tile_bins,
+                         const void *rows, const float *background3, float *out_img, float *final_Ts,
+                         int32_t *final_idx, const int32_t *tile_order, int32_t *tile_kmax, const float *depths,
+                         float *out_depth, const sgn_raster_opts *opts, sgn_stream_t stream);        // raster.hip
+int sgn_raster_views_bwd(int n_views, int n, int img_h, int img_w, const int32_t *ids, const int32_t *tile_bins,
+                         const void *rows, const float *conics, const float *logits, const float *background3,
+                         const float *final_Ts, const int32_t *final_idx, const float *v_out_img,
+                         const float *v_out_alpha, float alpha_clamp_bwd, float *v_xy, float *v_conic, float *v_colors,
+                         float *v_opacity, void *grad_ws, const int32_t *tile_order, const sgn_raster_opts *opts,
+                         sgn_stream_t stream, sgn_stream_t aux_stream);                            // raster.hip
+
 extern "C" __attribute__((visibility("default")))
 size_t sgn_rasterize_arena_bytes(int n, int64_t isect_capacity) {
     const size_t nn = (size_t)(n > 0 ? n : 1);
@@ -547,6 +564,171 @@ int sgn_rasterize_bwd_all(int img_h, int img_w, int block_width, int n, int64_t 
                                v_out_img, v_out_alpha, alpha_clamp_bwd, v_xy, v_conic, v_colors, v_opacity, recs_ws,
                                recs_ws_bytes, recs_packed, grad_ws, grad_ws_bytes, order, colors_pre_clamp, opts, stream,
                                aux_stream, first, last);
+}
+
+// ---------------------------------------------------------------- batched views, one call per direction
+// sgn_rasterize_views_fwd_all: sgn_rasterize_fwd_all's sequence over the rows of all n_views views at once — ONE depth
+// ranking, ONE host wait for the intersection count, ONE emission / tile sort / launch order over the n_views * tiles
+// tiles (tile id = view * tiles + local tile) and ONE launch of the forward kernels.  The count always travels through a
+// copy + event here (no mapped-word polling): one wait per batch either way.
+namespace {
+int views_args(const char *fn, int n_views, int n) {
+    if (n_views < 1 || n_views > SGN_VIEWS_MAX) {
+        sgn_set_error("%s: n_views %d outside [1, %d]", fn, n_views, SGN_VIEWS_MAX);
+        return -1;
+    }
+    if (n < 0 || (int64_t)n_views * (int64_t)n >= ((int64_t)1 << 28)) {
+        sgn_set_error("%s: n %d: need n >= 0 and n_views * n < 2^28", fn, n);
+        return -2;
+    }
+    return 0;
+}
+}  // namespace
+
+extern "C" __attribute__((visibility("default")))
+size_t sgn_rasterize_views_arena_bytes(int n_views, int n, int64_t isect_capacity) {
+    if (n_views < 1 || n_views > SGN_VIEWS_MAX || n < 0) return 0;
+    const int rows = n_views * n;
+    return sgn_rasterize_arena_bytes(rows, isect_capacity) + al256((size_t)(rows > 0 ? rows : 1) * 4);
+}
+
+extern "C" __attribute__((visibility("default")))
+int sgn_rasterize_views_fwd_all(int n_views, int n, const float *xys, const float *depths, const int32_t *radii,
+                                const float *conics, const float *colors, const float *opacity_logits, int cull,
+                                int img_h, int img_w, int block_width, const float *background3, int quadrant_masks,
+                                float *out_img, float *final_Ts, int32_t *final_idx, float *out_depth,
+                                int32_t *gaussian_ids_sorted, int64_t isect_capacity, int32_t *tile_bins,
+                                int32_t *tile_order, int32_t *tile_stats, void *rows, size_t rows_bytes,
+                                void *order_scratch, size_t order_scratch_bytes, void *arena, size_t arena_bytes,
+                                int32_t *count_pinned, int64_t *n_isect_host, int sort_rank_mode, int semantics,
+                                const sgn_raster_opts *opts, sgn_stream_t stream) {
+    if (int rc = views_args(__func__, n_views, n)) return rc;
+    if (block_width != 16 || img_h < 1 || img_w < 1) {
+        sgn_set_error("sgn_rasterize_views_fwd_all: needs block_width 16 and a positive image size");
+        return -3;
+    }
+    if (!n_isect_host || (n > 0 && (!xys || !depths || !radii || !conics || !colors || !opacity_logits ||
+                                    !background3 || !out_img || !final_Ts || !final_idx || !gaussian_ids_sorted ||
+                                    !tile_bins || !tile_order || !tile_stats || !rows || !arena))) {
+        sgn_set_error("sgn_rasterize_views_fwd_all: a required pointer is NULL");
+        return -4;
+    }
+    *n_isect_host = 0;
+    if (n == 0) return 0;
+    if (isect_capacity < 1 || isect_capacity >= ((int64_t)1 << 31)) {
+        sgn_set_error("sgn_rasterize_views_fwd_all: isect_capacity %lld", (long long)isect_capacity);
+        return -6;
+    }
+    const int R = n_views * n;
+    if (arena_bytes < sgn_rasterize_views_arena_bytes(n_views, n, isect_capacity) ||
+        rows_bytes < sgn_raster_workspace_bytes(R, 0, nullptr)) {
+        sgn_set_error("sgn_rasterize_views_fwd_all: arena or rows too small");
+        return -5;
+    }
+    sgn_raster_opts o;
+    sgn_raster_default_opts(&o);
+    if (opts) o = *opts;
+    hipStream_t s = (hipStream_t)stream;
+    const int tiles_x = (img_w + 15) / 16, tiles_y = (img_h + 15) / 16;
+    const int n_tiles = tiles_x * tiles_y * n_views;
+    char *p = (char *)arena;
+    int32_t *cum_r = (int32_t *)p; p += al256((size_t)R * 4);
+    int32_t *gid = (int32_t *)p; p += al256((size_t)R * 4);
+    float *bin_recs = (float *)p; p += al256((size_t)R * 32);
+    void *ws1 = p; const size_t ws1_bytes = sgn_bin_prepare_workspace_bytes(R); p += al256(ws1_bytes);
+    void *ws2 = p; const size_t ws2_bytes = sgn_bin_intersect_workspace_bytes(isect_capacity);
+    p += al256(ws2_bytes);
+    float *opac_rows = (float *)p;
+    int rc = sgn_views_repeat(n, n_views, opacity_logits, opac_rows, stream);
+    if (rc) return rc;
+    // first half of the binning over all rows: per-row tile counts on the one-view grid (every view shares it), the
+    // depth ranking of all rows, the scan in rank order
+    rc = sgn_bin_prepare_total(R, xys, depths, radii, cull ? conics : nullptr, cull ? opac_rows : nullptr, 1,
+                               cull ? 1 : 0, tiles_x, tiles_y, 16, cum_r, gid, 0, bin_recs, ws1, ws1_bytes,
+                               sort_rank_mode, nullptr, nullptr, nullptr, semantics, stream);
+    if (rc) return rc;
+    int32_t pageable = -1;
+    int32_t *dst = count_pinned ? count_pinned : &pageable;
+    hipEvent_t ev = nullptr;
+    hipError_t e = hipMemcpyAsync(dst, cum_r + (R - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && sync_event(&ev) != 0) e = hipErrorUnknown;
+    if (e == hipSuccess) e = hipEventRecord(ev, s);
+    if (e != hipSuccess) { sgn_set_error("sgn_rasterize_views_fwd_all: count read-back: %s", hipGetErrorString(e)); return (int)e; }
+    rc = sgn_raster_build_rows(R, xys, conics, colors, opac_rows, 1, 0, R, 0, rows, rows_bytes, nullptr, stream);
+    if (rc) return rc;
+    const bool stats_behind_bins = tile_stats == tile_bins + 2 * (size_t)n_tiles;
+    rc = sgn_bin_intersect_views(n_views, R, isect_capacity, bin_recs, cum_r, gid, tiles_x, tiles_y,
+                                 gaussian_ids_sorted, tile_bins, quadrant_masks, ws2, ws2_bytes, cum_r + (R - 1),
+                                 sort_rank_mode, stats_behind_bins ? 2 * n_tiles : 0, stream);
+    if (rc) return rc;
+    e = timed_event_sync(ev);                            // the batch's one host wait
+    if (e != hipSuccess) { sgn_set_error("sgn_rasterize_views_fwd_all: %s", hipGetErrorString(e)); return (int)e; }
+    const int64_t count = (int64_t)*(volatile int32_t *)dst;
+    *n_isect_host = count;
+    if (count > isect_capacity) return SGN_E_CAPACITY;
+    if (count < 1) return 0;
+    if (!stats_behind_bins) {
+        e = hipMemsetAsync(tile_stats, 0, sizeof(int32_t) * 2 * (size_t)n_tiles, s);
+        if (e != hipSuccess) { sgn_set_error("sgn_rasterize_views_fwd_all: %s", hipGetErrorString(e)); return (int)e; }
+    }
+    rc = sgn_tile_order(n_tiles, tile_bins, nullptr, o.adapt_fwd > 0 ? o.adapt_fwd : 1024, 0, tile_order, order_scratch,
+                        order_scratch_bytes, stream);
+    if (rc) return rc;
+    sgn_raster_opts oo = o;
+    oo.ids_qmask = quadrant_masks ? 1 : 0;
+    return sgn_raster_views_fwd(n_views, img_h, img_w, gaussian_ids_sorted, tile_bins, rows, background3, out_img,
+                                final_Ts, final_idx, tile_order, tile_stats, out_depth ? depths : nullptr, out_depth, &oo,
+                                stream);
+}
+
+extern "C" __attribute__((visibility("default")))
+int sgn_rasterize_views_bwd_all(int n_views, int n, int64_t n_isect, int img_h, int img_w,
+                                const int32_t *gaussian_ids_sorted, const int32_t *tile_bins, const int32_t *tile_stats,
+                                const float *conics, const float *opacity_logits, const float *background3,
+                                const float *final_Ts, const int32_t *final_idx, const float *v_out_img,
+                                const float *v_out_alpha, float alpha_clamp_bwd, float *v_xy, float *v_conic,
+                                float *v_colors, float *v_opacity_logits, const void *rows, size_t rows_bytes,
+                                void *grad_ws, size_t grad_ws_bytes, int32_t *tile_order, void *order_scratch,
+                                size_t order_scratch_bytes, int small_q16, const sgn_raster_opts *opts,
+                                sgn_stream_t stream, sgn_stream_t aux_stream) {
+    if (int rc = views_args(__func__, n_views, n)) return rc;
+    if (img_h < 1 || img_w < 1 || !(alpha_clamp_bwd > 0.f && alpha_clamp_bwd < 1.f)) {
+        sgn_set_error("sgn_rasterize_views_bwd_all: bad image size or alpha clamp");
+        return -3;
+    }
+    if (n == 0) return 0;
+    if (!conics || !opacity_logits || !v_xy || !v_conic || !v_colors || !v_opacity_logits || !grad_ws || !rows ||
+        (n_isect > 0 && (!gaussian_ids_sorted || !tile_bins || !tile_stats || !tile_order || !background3 ||
+                         !final_Ts || !final_idx || !v_out_alpha))) {
+        sgn_set_error("sgn_rasterize_views_bwd_all: a required pointer is NULL");
+        return -4;
+    }
+    const int R = n_views * n;
+    if (grad_ws_bytes < sgn_raster_bwd_workspace_bytes(R) || rows_bytes < sgn_raster_workspace_bytes(R, 0, nullptr)) {
+        sgn_set_error("sgn_rasterize_views_bwd_all: workspace too small");
+        return -5;
+    }
+    if (n_isect < 0 || n_isect >= ((int64_t)1 << 31)) {
+        sgn_set_error("sgn_rasterize_views_bwd_all: n_isect %lld", (long long)n_isect);
+        return -6;
+    }
+    sgn_raster_opts o;
+    sgn_raster_default_opts(&o);
+    if (opts) o = *opts;
+    const int n_tiles = ((img_w + 15) / 16) * ((img_h + 15) / 16) * n_views;
+    if (n_isect > 0) {
+        int rc = sgn_tile_order(n_tiles, tile_bins, tile_stats, o.adapt_bwd > 0 ? o.adapt_bwd : 256, small_q16,
+                                tile_order, order_scratch, order_scratch_bytes, stream);
+        if (rc) return rc;
+    } else {
+        // nothing was listed: every gradient is zero (the walks find empty lists; the unpack writes zeros)
+        const hipError_t e = hipMemsetAsync(tile_order, 0, sizeof(int32_t) * ((size_t)n_tiles + 2), (hipStream_t)stream);
+        if (e != hipSuccess) { sgn_set_error("sgn_rasterize_views_bwd_all: %s", hipGetErrorString(e)); return (int)e; }
+    }
+    return sgn_raster_views_bwd(n_views, n, img_h, img_w, gaussian_ids_sorted, tile_bins, rows, conics,
+                                opacity_logits, background3, final_Ts, final_idx, v_out_img, v_out_alpha,
+                                alpha_clamp_bwd, v_xy, v_conic, v_colors, v_opacity_logits, grad_ws, tile_order, opts,
+                                stream, aux_stream);
 }
 
 // ---------------------------------------------------------------- kernel timing (bench/profiles)

@@ -334,34 +334,48 @@ struct NoOut {
 };
 // TK = tile-key type: uint16_t whenever the image has at most 65536 tiles (1920x1280/16 = 9600), which takes a
 // quarter of the bytes off the emission and off every pass of the tile sort; uint32_t otherwise.
-template <typename TK>
+// KM: the tile key of an emitted pair.  NoKeyMap keeps the local tile (one image); ViewKeyMap (batched views) adds the
+// first tile of the row's view: row r = b * n_per_view + i belongs to view b (ids below 2^28, quadrant masks above).
+struct NoKeyMap {
+    __device__ __forceinline__ uint32_t operator()(uint32_t key, int32_t) const { return key; }
+};
+struct ViewKeyMap {
+    uint32_t n_per_view, tiles_per_view;
+    __device__ __forceinline__ uint32_t operator()(uint32_t key, int32_t val) const {
+        return key + (((uint32_t)val & 0x0FFFFFFFu) / n_per_view) * tiles_per_view;
+    }
+};
+template <typename TK, class KM = NoKeyMap>
 struct GlobalOut {
     TK *__restrict__ tkeys;
     int32_t *__restrict__ tvals;
+    KM km;
     __device__ __forceinline__ void operator()(int pos, uint32_t key, int32_t val) const {
-        tkeys[pos] = (TK)key;
+        tkeys[pos] = (TK)km(key, val);
         tvals[pos] = val;
     }
 };
-template <typename TK>
+template <typename TK, class KM = NoKeyMap>
 struct BoundedOut {       // a speculative launch whose buffers turn out too small: never write past `cap` slots
     TK *__restrict__ tkeys;
     int32_t *__restrict__ tvals;
     int cap;
+    KM km;
     __device__ __forceinline__ void operator()(int pos, uint32_t key, int32_t val) const {
         if (pos < cap) {
-            tkeys[pos] = (TK)key;
+            tkeys[pos] = (TK)km(key, val);
             tvals[pos] = val;
         }
     }
 };
-template <typename TK>
+template <typename TK, class KM = NoKeyMap>
 struct LdsOut {          // wave-local staging: positions relative to the wave's first output slot
     TK *keys;
     int32_t *vals;
     int base;
+    KM km;
     __device__ __forceinline__ void operator()(int pos, uint32_t key, int32_t val) const {
-        keys[pos - base] = (TK)key;
+        keys[pos - base] = (TK)km(key, val);
         vals[pos - base] = val;
     }
 };
@@ -532,16 +546,14 @@ __global__ __launch_bounds__(256) void bin_count_kernel(int n, const float *__re
 // entries the pairs are staged in LDS and written out with full-width coalesced stores (per-lane sequential
 // dword stores cost one memory request each: 16.6 M requests per view on the benchmark scene).
 constexpr int EMIT_CAP = 1024;
-template <typename TK>
-__global__ __launch_bounds__(64) void bin_emit_kernel(int n, const int32_t *__restrict__ gid_by_rank,
+template <typename TK, class KM>
+__device__ __forceinline__ void bin_emit_body(int n, const int32_t *__restrict__ gid_by_rank,
                                                       const int32_t *__restrict__ cum_r,
                                                       const BinRec *__restrict__ recs, int tiles_x, int tiles_y,
                                                       int block, TK *__restrict__ tkeys,
                                                       int32_t *__restrict__ tvals, int cap,
-                                                      int32_t *__restrict__ zero_buf, int zero_n, int qmask) {
-    __shared__ TK lk[EMIT_CAP];
-    __shared__ int32_t lv[EMIT_CAP];
-    __shared__ FlatScratch scratch;
+                                                      int32_t *__restrict__ zero_buf, int zero_n, int qmask, KM km,
+                                              TK *lk, int32_t *lv, FlatScratch &scratch) {
     const int lane = threadIdx.x;
     // tile_bins must read 0 for tiles without entries and tile_bins32_kernel (two launches later on this stream)
     // only writes the tiles that have some: cleared here instead of by a memset launch of its own (~5 us each)
@@ -568,17 +580,48 @@ __global__ __launch_bounds__(64) void bin_emit_kernel(int n, const int32_t *__re
     }
     const Ellipse E = make_ellipse(gx, gy, a, b, c, s);
     if (base + total > cap) {                                 // wave-uniform; only a mis-sized speculative launch
-        tiles_of<true>(live, E, mnx, mny, mxx, mxy, gid, base, tiles_x, block, scratch, BoundedOut<TK>{tkeys, tvals, cap}, qmask);
+        tiles_of<true>(live, E, mnx, mny, mxx, mxy, gid, base, tiles_x, block, scratch, BoundedOut<TK, KM>{tkeys, tvals, cap, km}, qmask);
     } else if (total <= EMIT_CAP) {
-        tiles_of<true>(live, E, mnx, mny, mxx, mxy, gid, base, tiles_x, block, scratch, LdsOut<TK>{lk, lv, base}, qmask);
+        tiles_of<true>(live, E, mnx, mny, mxx, mxy, gid, base, tiles_x, block, scratch, LdsOut<TK, KM>{lk, lv, base, km}, qmask);
         __syncthreads();                                      // single-wave workgroup: a fence, no s_barrier
         for (int j = lane; j < total; j += 64) {
             tkeys[base + j] = lk[j];
             tvals[base + j] = lv[j];
         }
     } else {
-        tiles_of<true>(live, E, mnx, mny, mxx, mxy, gid, base, tiles_x, block, scratch, GlobalOut<TK>{tkeys, tvals}, qmask);
+        tiles_of<true>(live, E, mnx, mny, mxx, mxy, gid, base, tiles_x, block, scratch, GlobalOut<TK, KM>{tkeys, tvals, km}, qmask);
     }
+}
+
+template <typename TK>
+__global__ __launch_bounds__(64) void bin_emit_kernel(int n, const int32_t *__restrict__ gid_by_rank,
+                                                      const int32_t *__restrict__ cum_r,
+                                                      const BinRec *__restrict__ recs, int tiles_x, int tiles_y,
+                                                      int block, TK *__restrict__ tkeys,
+                                                      int32_t *__restrict__ tvals, int cap,
+                                                      int32_t *__restrict__ zero_buf, int zero_n, int qmask) {
+    __shared__ TK lk[EMIT_CAP];
+    __shared__ int32_t lv[EMIT_CAP];
+    __shared__ FlatScratch scratch;
+    bin_emit_body<TK>(n, gid_by_rank, cum_r, recs, tiles_x, tiles_y, block, tkeys, tvals, cap, zero_buf, zero_n, qmask,
+                      NoKeyMap{}, lk, lv, scratch);
+}
+
+// batched views: rows of all views in one depth ranking, each pair keyed to its view's own tiles (ViewKeyMap); the tile
+// boxes are clamped to the one-view grid tiles_x x tiles_y, which every view shares
+template <typename TK>
+__global__ __launch_bounds__(64) void bin_emit_views_kernel(int n, const int32_t *__restrict__ gid_by_rank,
+                                                            const int32_t *__restrict__ cum_r,
+                                                            const BinRec *__restrict__ recs, int tiles_x, int tiles_y,
+                                                            int block, TK *__restrict__ tkeys,
+                                                            int32_t *__restrict__ tvals, int cap,
+                                                            int32_t *__restrict__ zero_buf, int zero_n, int qmask,
+                                                            ViewKeyMap km) {
+    __shared__ TK lk[EMIT_CAP];
+    __shared__ int32_t lv[EMIT_CAP];
+    __shared__ FlatScratch scratch;
+    bin_emit_body<TK>(n, gid_by_rank, cum_r, recs, tiles_x, tiles_y, block, tkeys, tvals, cap, zero_buf, zero_n, qmask,
+                      km, lk, lv, scratch);
 }
 
 // ---- launch-order helpers (tile_order_kernel further down)
@@ -928,18 +971,23 @@ SGN_EXPORT int sgn_bin_intersect(int n, int64_t n_isect, const float *bin_record
                                   sort_rank_mode, 0, stream);
 }
 
-int sgn_bin_intersect_zero(int n, int64_t n_isect, const float *bin_records, const int32_t *cum_by_rank,
-                           const int32_t *gid_by_rank, int tiles_x, int tiles_y, int block_width,
-                           int32_t *gaussian_ids_sorted, int32_t *tile_bins, int quadrant_masks, void *ws,
-                           size_t ws_bytes, const int32_t *n_isect_dev, int sort_rank_mode, int also_zero_words,
-                           sgn_stream_t stream) {
+// n_views = 0: one image (bin_emit_kernel); n_views >= 1: n = n_views * n_per_view rows, tile id = view * tiles_x *
+// tiles_y + local tile (bin_emit_views_kernel), tile_bins holds n_views * tiles_x * tiles_y entries
+static int bin_intersect_impl(int n_views, int n, int64_t n_isect, const float *bin_records, const int32_t *cum_by_rank,
+                              const int32_t *gid_by_rank, int tiles_x, int tiles_y, int block_width,
+                              int32_t *gaussian_ids_sorted, int32_t *tile_bins, int quadrant_masks, void *ws,
+                              size_t ws_bytes, const int32_t *n_isect_dev, int sort_rank_mode, int also_zero_words,
+                              sgn_stream_t stream) {
     SGN_ARG_CHECK(also_zero_words >= 0, -7);
     SGN_ARG_CHECK(n >= 0 && n_isect >= 0 && n_isect < ((int64_t)1 << 31), -1);
     SGN_ARG_CHECK(block_width >= 2 && block_width <= 16 && tiles_x > 0 && tiles_y > 0, -2);
     SGN_ARG_CHECK(tile_bins != nullptr, -3);
     SGN_ARG_CHECK(!quadrant_masks || (block_width == 16 && n < SGN_QMASK_MAX_IDS), -6);
     hipStream_t s = (hipStream_t)stream;
-    const int n_tiles = tiles_x * tiles_y;
+    SGN_ARG_CHECK(n_views >= 0 && n_views <= SGN_VIEWS_MAX && (n_views == 0 || n % n_views == 0), -8);
+    const int tiles_per_view = tiles_x * tiles_y;
+    const int n_tiles = tiles_per_view * (n_views > 0 ? n_views : 1);
+    const ViewKeyMap km{(uint32_t)(n_views > 0 ? n / n_views : 1), (uint32_t)tiles_per_view};
     if (n_isect == 0 || n == 0) {
         SGN_HIP_CHECK(hipMemsetAsync(tile_bins, 0, ((size_t)n_tiles * 2 + also_zero_words) * sizeof(int32_t), s));
         return 0;
@@ -956,9 +1004,14 @@ int sgn_bin_intersect_zero(int n, int64_t n_isect, const float *bin_records, con
     if (n_tiles <= 65536) {       // 16-bit tile keys (the buffers keep their 4-byte-per-key size)
         uint16_t *k16 = (uint16_t *)tkeys, *k16s = (uint16_t *)tkeys_sorted;
         sgn_timing_begin(SGN_T_MAP, s);
-        hipLaunchKernelGGL(bin_emit_kernel<uint16_t>, dim3(sgn_cdiv(n, 64)), dim3(64), 0, s, n, gid_by_rank, cum_by_rank,
-                           recs, tiles_x, tiles_y, block_width, k16, tvals, (int)n_isect, tile_bins, 2 * n_tiles + also_zero_words,
-                           quadrant_masks);
+        if (n_views > 0)
+            hipLaunchKernelGGL(bin_emit_views_kernel<uint16_t>, dim3(sgn_cdiv(n, 64)), dim3(64), 0, s, n, gid_by_rank,
+                               cum_by_rank, recs, tiles_x, tiles_y, block_width, k16, tvals, (int)n_isect, tile_bins,
+                               2 * n_tiles + also_zero_words, quadrant_masks, km);
+        else
+            hipLaunchKernelGGL(bin_emit_kernel<uint16_t>, dim3(sgn_cdiv(n, 64)), dim3(64), 0, s, n, gid_by_rank, cum_by_rank,
+                               recs, tiles_x, tiles_y, block_width, k16, tvals, (int)n_isect, tile_bins,
+                               2 * n_tiles + also_zero_words, quadrant_masks);
         sgn_timing_end(SGN_T_MAP, s);
         sgn_timing_begin(SGN_T_SORT, s);
         sgn_sort_pairs16_launch((uint32_t)n_isect, tile_bits, k16, tvals, k16s, gaussian_ids_sorted, sort_ws, s,
@@ -970,9 +1023,14 @@ int sgn_bin_intersect_zero(int n, int64_t n_isect, const float *bin_records, con
         sgn_timing_end(SGN_T_BINS, s);
     } else {
         sgn_timing_begin(SGN_T_MAP, s);
-        hipLaunchKernelGGL(bin_emit_kernel<uint32_t>, dim3(sgn_cdiv(n, 64)), dim3(64), 0, s, n, gid_by_rank, cum_by_rank,
-                           recs, tiles_x, tiles_y, block_width, tkeys, tvals, (int)n_isect, tile_bins, 2 * n_tiles + also_zero_words,
-                           quadrant_masks);
+        if (n_views > 0)
+            hipLaunchKernelGGL(bin_emit_views_kernel<uint32_t>, dim3(sgn_cdiv(n, 64)), dim3(64), 0, s, n, gid_by_rank,
+                               cum_by_rank, recs, tiles_x, tiles_y, block_width, tkeys, tvals, (int)n_isect, tile_bins,
+                               2 * n_tiles + also_zero_words, quadrant_masks, km);
+        else
+            hipLaunchKernelGGL(bin_emit_kernel<uint32_t>, dim3(sgn_cdiv(n, 64)), dim3(64), 0, s, n, gid_by_rank, cum_by_rank,
+                               recs, tiles_x, tiles_y, block_width, tkeys, tvals, (int)n_isect, tile_bins,
+                               2 * n_tiles + also_zero_words, quadrant_masks);
         sgn_timing_end(SGN_T_MAP, s);
         sgn_timing_begin(SGN_T_SORT, s);
         sgn_sort_pairs32_launch((uint32_t)n_isect, tile_bits, tkeys, tvals, tkeys_sorted, gaussian_ids_sorted, sort_ws,
@@ -985,6 +1043,27 @@ int sgn_bin_intersect_zero(int n, int64_t n_isect, const float *bin_records, con
     }
     SGN_LAUNCH_CHECK();
     return 0;
+}
+
+int sgn_bin_intersect_zero(int n, int64_t n_isect, const float *bin_records, const int32_t *cum_by_rank,
+                           const int32_t *gid_by_rank, int tiles_x, int tiles_y, int block_width,
+                           int32_t *gaussian_ids_sorted, int32_t *tile_bins, int quadrant_masks, void *ws,
+                           size_t ws_bytes, const int32_t *n_isect_dev, int sort_rank_mode, int also_zero_words,
+                           sgn_stream_t stream) {
+    return bin_intersect_impl(0, n, n_isect, bin_records, cum_by_rank, gid_by_rank, tiles_x, tiles_y, block_width,
+                              gaussian_ids_sorted, tile_bins, quadrant_masks, ws, ws_bytes, n_isect_dev, sort_rank_mode,
+                              also_zero_words, stream);
+}
+
+// batched views (api.cpp sgn_rasterize_views_fwd_all): n = n_views * n_per_view rows of one depth ranking
+int sgn_bin_intersect_views(int n_views, int n, int64_t n_isect, const float *bin_records, const int32_t *cum_by_rank,
+                            const int32_t *gid_by_rank, int tiles_x, int tiles_y, int32_t *gaussian_ids_sorted,
+                            int32_t *tile_bins, int quadrant_masks, void *ws, size_t ws_bytes,
+                            const int32_t *n_isect_dev, int sort_rank_mode, int also_zero_words, sgn_stream_t stream) {
+    SGN_ARG_CHECK(n_views >= 1, -8);
+    return bin_intersect_impl(n_views, n, n_isect, bin_records, cum_by_rank, gid_by_rank, tiles_x, tiles_y, 16,
+                              gaussian_ids_sorted, tile_bins, quadrant_masks, ws, ws_bytes, n_isect_dev, sort_rank_mode,
+                              also_zero_words, stream);
 }
 
 // ------------------------------------------------------------------------------------------ window recognition

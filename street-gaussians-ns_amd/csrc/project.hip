@@ -99,36 +99,13 @@ __device__ __forceinline__ Loaded load_gaussian(int i, const float *__restrict__
     return L;
 }
 
-template <int FUSED>
-__global__ __launch_bounds__(256) void project_fwd_kernel(
-    int n, const float *__restrict__ means, const float *__restrict__ scales,
-    const float *__restrict__ quats, Cam cam, Fuse fuse, float *__restrict__ cov3d, float *__restrict__ xys,
-    float *__restrict__ depths, int32_t *__restrict__ radii, float *__restrict__ conics,
-    float *__restrict__ comp, int32_t *__restrict__ num_tiles_hit, QuatCheck qc) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    float V[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) V[k] = cam.V[k];
-    const Loaded LG = load_gaussian<FUSED>(i, means, scales, quats, cam.glob_scale, fuse);
-    if constexpr (FUSED == 0) {
-        // upstream's `quats must be normalized` assertion riding the projection (sgn_project_fwd_all): the quaternion is
-        // in registers anyway.  Same one-sided test as check_unit_quats_kernel below; a failing row STAMPS the flag
-        // (every writer stores the same value: benign race), so a flag that was zero once needs no clear per call.
-        if (qc.flag != nullptr) {
-            const float nrm = sqrtf(LG.q[0] * LG.q[0] + LG.q[1] * LG.q[1] + LG.q[2] * LG.q[2] + LG.q[3] * LG.q[3]);
-            // system scope: the flag may live in mapped pinned HOST memory (sgn_project_fwd_all), where the host reads it
-            // behind an event without a copy command (ADVICE r05: a plain store is not guaranteed to have landed)
-            if (!(nrm - 1.f < qc.tol)) {
-                __hip_atomic_store(qc.flag, qc.stamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                __threadfence_system();
-            }
-            if (qc.ok != nullptr && i == 0) {
-                __hip_atomic_store(qc.ok, qc.stamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                __threadfence_system();
-            }
-        }
-    }
+// The per-camera part of the forward: the Gaussian as loaded, one camera (view matrix V, intrinsics and tile grid in
+// `cam`), output row `o`.  project_fwd_kernel calls it once (o = i), project_views_fwd_kernel once per view.
+__device__ __forceinline__ void project_fwd_row(const Loaded LG, const float (&V)[12], const Cam cam, int o,
+                                                float *cov3d, float *xys,
+                                                float *depths, int32_t *radii,
+                                                float *conics, float *comp,
+                                                int32_t *num_tiles_hit) {
     const float p0 = LG.p[0], p1 = LG.p[1], p2 = LG.p[2];
     const float pvx = V[0] * p0 + V[1] * p1 + V[2] * p2 + V[3];
     const float pvy = V[4] * p0 + V[5] * p1 + V[6] * p2 + V[7];
@@ -199,14 +176,179 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
         }
     }
 #pragma unroll
-    for (int k = 0; k < 6; ++k) cov3d[6 * i + k] = o_cov[k];
-    xys[2 * i] = o_x; xys[2 * i + 1] = o_y;
-    depths[i] = o_d;
-    radii[i] = o_r;
+    for (int k = 0; k < 6; ++k) cov3d[6 * o + k] = o_cov[k];
+    xys[2 * o] = o_x; xys[2 * o + 1] = o_y;
+    depths[o] = o_d;
+    radii[o] = o_r;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) conics[3 * i + k] = o_con[k];
-    comp[i] = o_comp;
-    num_tiles_hit[i] = o_n;
+    for (int k = 0; k < 3; ++k) conics[3 * o + k] = o_con[k];
+    comp[o] = o_comp;
+    num_tiles_hit[o] = o_n;
+}
+
+template <int FUSED>
+__global__ __launch_bounds__(256) void project_fwd_kernel(
+    int n, const float *__restrict__ means, const float *__restrict__ scales,
+    const float *__restrict__ quats, Cam cam, Fuse fuse, float *__restrict__ cov3d, float *__restrict__ xys,
+    float *__restrict__ depths, int32_t *__restrict__ radii, float *__restrict__ conics,
+    float *__restrict__ comp, int32_t *__restrict__ num_tiles_hit, QuatCheck qc) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float V[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) V[k] = cam.V[k];
+    const Loaded LG = load_gaussian<FUSED>(i, means, scales, quats, cam.glob_scale, fuse);
+    if constexpr (FUSED == 0) {
+        // upstream's `quats must be normalized` assertion riding the projection (sgn_project_fwd_all): the quaternion is
+        // in registers anyway.  Same one-sided test as check_unit_quats_kernel below; a failing row STAMPS the flag
+        // (every writer stores the same value: benign race), so a flag that was zero once needs no clear per call.
+        if (qc.flag != nullptr) {
+            const float nrm = sqrtf(LG.q[0] * LG.q[0] + LG.q[1] * LG.q[1] + LG.q[2] * LG.q[2] + LG.q[3] * LG.q[3]);
+            // system scope: the flag may live in mapped pinned HOST memory (sgn_project_fwd_all), where the host reads it
+            // behind an event without a copy command (ADVICE r05: a plain store is not guaranteed to have landed)
+            if (!(nrm - 1.f < qc.tol)) {
+                __hip_atomic_store(qc.flag, qc.stamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                __threadfence_system();
+            }
+            if (qc.ok != nullptr && i == 0) {
+                __hip_atomic_store(qc.ok, qc.stamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                __threadfence_system();
+            }
+        }
+    }
+    project_fwd_row(LG, V, cam, i, cov3d, xys, depths, radii, conics, comp, num_tiles_hit);
+}
+
+// The per-camera part of the backward (row `o` of the forward's outputs and of the incoming gradients, the Gaussian as
+// loaded, one camera): world-frame d/d mean, d/d scale and d/d quaternion before the fused front end's chain rules,
+// and the 2D / 3D covariance gradients.  project_bwd_kernel calls it once (o = i), project_views_bwd_kernel once per
+// view that sees the Gaussian.
+__device__ __forceinline__ void project_bwd_row(int o, const Loaded LG, const float (&V)[12], const Cam cam,
+                                                const float *cov3d, const float *conics,
+                                                const float *comp, const float *v_xy,
+                                                const float *v_depth, const float *v_conic,
+                                                const float *v_comp, float (&o_vm)[3], float (&o_vs)[3],
+                                                float (&o_vq)[4], float (&o_vc2)[3], float (&o_vc3)[6]) {
+    const float fx = cam.fx, fy = cam.fy;
+    const float p0 = LG.p[0], p1 = LG.p[1], p2 = LG.p[2];
+    const float pvx = V[0] * p0 + V[1] * p1 + V[2] * p2 + V[3];
+    const float pvy = V[4] * p0 + V[5] * p1 + V[6] * p2 + V[7];
+    const float pvz = V[8] * p0 + V[9] * p1 + V[10] * p2 + V[11];
+    const float rw = 1.f / (pvz + 1e-6f);
+    const float vpx = fx * v_xy[2 * o], vpy = fy * v_xy[2 * o + 1];
+    const float vv0 = vpx * rw, vv1 = vpy * rw, vv2 = -(vpx * pvx + vpy * pvy) * rw * rw;
+    float vm[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) vm[j] = V[j] * vv0 + V[4 + j] * vv1 + V[8 + j] * vv2;
+    const float vz = v_depth ? v_depth[o] : 0.f;      // NULL: depths took no part in the loss
+    vm[0] += V[8] * vz; vm[1] += V[9] * vz; vm[2] += V[10] * vz;
+
+    const float X00 = conics[3 * o], X01 = conics[3 * o + 1], X11 = conics[3 * o + 2];
+    // v_conic[:,1] is the true dL/d(conic.y); the symmetric matrix gradient carries half of it per slot (exact)
+    const float g0 = v_conic[3 * o], g1 = 0.5f * v_conic[3 * o + 1], g2 = v_conic[3 * o + 2];
+    const float A00 = X00 * g0 + X01 * g1, A01 = X00 * g1 + X01 * g2;
+    const float A10 = X01 * g0 + X11 * g1, A11 = X01 * g1 + X11 * g2;
+    const float S00 = -(A00 * X00 + A01 * X01), S01 = -(A00 * X01 + A01 * X11);
+    const float S10 = -(A10 * X00 + A11 * X01), S11 = -(A10 * X01 + A11 * X11);
+    float vc2[3] = {S00, S01 + S10, S11};
+    if (v_comp != nullptr) {
+        const float cmp = comp[o];
+        const float inv_det = X00 * X11 - X01 * X01;
+        const float om = 1.f - cmp * cmp;
+        const float vsq = v_comp[o] * 0.5f / (cmp + 1e-6f);
+        vc2[0] += vsq * (om * X00 - 0.3f * inv_det);
+        vc2[1] += 2.f * vsq * (om * X01);
+        vc2[2] += vsq * (om * X11 - 0.3f * inv_det);
+    }
+    o_vc2[0] = vc2[0]; o_vc2[1] = vc2[1]; o_vc2[2] = vc2[2];
+
+    const float rz = 1.f / pvz, rz2 = rz * rz, rz3 = rz2 * rz;
+    // default: upstream CUDA's project_cov3d_ewa_vjp — the Jacobian of the UN-clamped view-space point.  Variant
+    // (SGN_SEM_EWA_VJP_CLAMPED): differentiate through the forward's clamp tx = tz * clamp(pvx / tz, +-lim): where
+    // the clamp is active d tx / d pvx = 0 and d tx / d tz = tx / tz (what autograd through _torch_impl gives)
+    float ex = pvx, ey = pvy;
+    bool clx = false, cly = false;
+    if (cam.sem & SGN_SEM_EWA_VJP_CLAMPED) {
+        const float qx = pvx / pvz, qy = pvy / pvz;
+        clx = !(qx <= cam.lim_x && qx >= -cam.lim_x);
+        cly = !(qy <= cam.lim_y && qy >= -cam.lim_y);
+        ex = pvz * fminf(cam.lim_x, fmaxf(-cam.lim_x, qx));
+        ey = pvz * fminf(cam.lim_y, fmaxf(-cam.lim_y, qy));
+    }
+    const float J00 = fx * rz, J02 = -fx * ex * rz2, J11 = fy * rz, J12 = -fy * ey * rz2;
+    float T[2][3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        T[0][j] = J00 * V[j] + J02 * V[8 + j];
+        T[1][j] = J11 * V[4 + j] + J12 * V[8 + j];
+    }
+    const float c0 = cov3d[6 * o], c1 = cov3d[6 * o + 1], c2 = cov3d[6 * o + 2];
+    const float c3 = cov3d[6 * o + 3], c4 = cov3d[6 * o + 4], c5 = cov3d[6 * o + 5];
+    const float S[3][3] = {{c0, c1, c2}, {c1, c3, c4}, {c2, c4, c5}};
+    const float G[2][2] = {{vc2[0], 0.5f * vc2[1]}, {0.5f * vc2[1], vc2[2]}};
+    float GT[2][3];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) GT[a][j] = G[a][0] * T[0][j] + G[a][1] * T[1][j];
+    float vS[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) vS[a][b] = T[0][a] * GT[0][b] + T[1][a] * GT[1][b];
+    o_vc3[0] = vS[0][0]; o_vc3[1] = vS[0][1] + vS[1][0]; o_vc3[2] = vS[0][2] + vS[2][0];
+    o_vc3[3] = vS[1][1]; o_vc3[4] = vS[1][2] + vS[2][1]; o_vc3[5] = vS[2][2];
+    float vT[2][3];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            vT[a][j] = 2.f * (GT[a][0] * S[0][j] + GT[a][1] * S[1][j] + GT[a][2] * S[2][j]);
+    const float vJ00 = vT[0][0] * V[0] + vT[0][1] * V[1] + vT[0][2] * V[2];
+    const float vJ02 = vT[0][0] * V[8] + vT[0][1] * V[9] + vT[0][2] * V[10];
+    const float vJ11 = vT[1][0] * V[4] + vT[1][1] * V[5] + vT[1][2] * V[6];
+    const float vJ12 = vT[1][0] * V[8] + vT[1][1] * V[9] + vT[1][2] * V[10];
+    const float vt0 = clx ? 0.f : -fx * rz2 * vJ02, vt1 = cly ? 0.f : -fy * rz2 * vJ12;
+    // d J02 / d tz = 2 fx tx / tz^3 with tx free, fx tx / tz^3 with tx = tz * lim (clamped)
+    const float vt2 = -fx * rz2 * vJ00 + (clx ? 1.f : 2.f) * fx * ex * rz3 * vJ02 - fy * rz2 * vJ11 +
+                      (cly ? 1.f : 2.f) * fy * ey * rz3 * vJ12;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) vm[j] += V[j] * vt0 + V[4 + j] * vt1 + V[8 + j] * vt2;
+    o_vm[0] = vm[0]; o_vm[1] = vm[1]; o_vm[2] = vm[2];
+
+    const float vV[3][3] = {{o_vc3[0], 0.5f * o_vc3[1], 0.5f * o_vc3[2]},
+                            {0.5f * o_vc3[1], o_vc3[3], 0.5f * o_vc3[4]},
+                            {0.5f * o_vc3[2], 0.5f * o_vc3[4], o_vc3[5]}};
+    const float w = LG.q[0], x = LG.q[1], y = LG.q[2], z = LG.q[3];
+    float R[3][3], M[3][3], sc[3];
+    quat_to_R(w, x, y, z, R);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        sc[c] = LG.s[c];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) M[r][c] = R[r][c] * sc[c];
+    }
+    float vM[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            vM[a][c] = 2.f * (vV[a][0] * M[0][c] + vV[a][1] * M[1][c] + vV[a][2] * M[2][c]);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        o_vs[c] = (R[0][c] * vM[0][c] + R[1][c] * vM[1][c] + R[2][c] * vM[2][c]) * cam.glob_scale;
+    float vR[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) vR[a][c] = vM[a][c] * sc[c];
+    o_vq[0] = 2.f * (x * (vR[2][1] - vR[1][2]) + y * (vR[0][2] - vR[2][0]) + z * (vR[1][0] - vR[0][1]));
+    o_vq[1] = 2.f * (-2.f * x * (vR[1][1] + vR[2][2]) + y * (vR[1][0] + vR[0][1]) +
+                     z * (vR[2][0] + vR[0][2]) + w * (vR[2][1] - vR[1][2]));
+    o_vq[2] = 2.f * (x * (vR[1][0] + vR[0][1]) - 2.f * y * (vR[0][0] + vR[2][2]) +
+                     z * (vR[2][1] + vR[1][2]) + w * (vR[0][2] - vR[2][0]));
+    o_vq[3] = 2.f * (x * (vR[2][0] + vR[0][2]) + y * (vR[2][1] + vR[1][2]) -
+                     2.f * z * (vR[0][0] + vR[1][1]) + w * (vR[1][0] - vR[0][1]));
 }
 
 // Pose gradient of the fused front end (POSE = true): per-wave partial sums of the 16 pose-table terms, one slot per
@@ -242,127 +384,9 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
         float V[12];
 #pragma unroll
         for (int k = 0; k < 12; ++k) V[k] = cam.V[k];
-        const float fx = cam.fx, fy = cam.fy;
         const Loaded LG = load_gaussian<FUSED>(i, means, scales, quats, cam.glob_scale, fuse);
-        const float p0 = LG.p[0], p1 = LG.p[1], p2 = LG.p[2];
-        const float pvx = V[0] * p0 + V[1] * p1 + V[2] * p2 + V[3];
-        const float pvy = V[4] * p0 + V[5] * p1 + V[6] * p2 + V[7];
-        const float pvz = V[8] * p0 + V[9] * p1 + V[10] * p2 + V[11];
-        const float rw = 1.f / (pvz + 1e-6f);
-        const float vpx = fx * v_xy[2 * i], vpy = fy * v_xy[2 * i + 1];
-        const float vv0 = vpx * rw, vv1 = vpy * rw, vv2 = -(vpx * pvx + vpy * pvy) * rw * rw;
-        float vm[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) vm[j] = V[j] * vv0 + V[4 + j] * vv1 + V[8 + j] * vv2;
-        const float vz = v_depth ? v_depth[i] : 0.f;      // NULL: depths took no part in the loss
-        vm[0] += V[8] * vz; vm[1] += V[9] * vz; vm[2] += V[10] * vz;
-
-        const float X00 = conics[3 * i], X01 = conics[3 * i + 1], X11 = conics[3 * i + 2];
-        // v_conic[:,1] is the true dL/d(conic.y); the symmetric matrix gradient carries half of it per slot (exact)
-        const float g0 = v_conic[3 * i], g1 = 0.5f * v_conic[3 * i + 1], g2 = v_conic[3 * i + 2];
-        const float A00 = X00 * g0 + X01 * g1, A01 = X00 * g1 + X01 * g2;
-        const float A10 = X01 * g0 + X11 * g1, A11 = X01 * g1 + X11 * g2;
-        const float S00 = -(A00 * X00 + A01 * X01), S01 = -(A00 * X01 + A01 * X11);
-        const float S10 = -(A10 * X00 + A11 * X01), S11 = -(A10 * X01 + A11 * X11);
-        float vc2[3] = {S00, S01 + S10, S11};
-        if (v_comp != nullptr) {
-            const float cmp = comp[i];
-            const float inv_det = X00 * X11 - X01 * X01;
-            const float om = 1.f - cmp * cmp;
-            const float vsq = v_comp[i] * 0.5f / (cmp + 1e-6f);
-            vc2[0] += vsq * (om * X00 - 0.3f * inv_det);
-            vc2[1] += 2.f * vsq * (om * X01);
-            vc2[2] += vsq * (om * X11 - 0.3f * inv_det);
-        }
-        o_vc2[0] = vc2[0]; o_vc2[1] = vc2[1]; o_vc2[2] = vc2[2];
-
-        const float rz = 1.f / pvz, rz2 = rz * rz, rz3 = rz2 * rz;
-        // default: upstream CUDA's project_cov3d_ewa_vjp — the Jacobian of the UN-clamped view-space point.  Variant
-        // (SGN_SEM_EWA_VJP_CLAMPED): differentiate through the forward's clamp tx = tz * clamp(pvx / tz, +-lim): where
-        // the clamp is active d tx / d pvx = 0 and d tx / d tz = tx / tz (what autograd through _torch_impl gives)
-        float ex = pvx, ey = pvy;
-        bool clx = false, cly = false;
-        if (cam.sem & SGN_SEM_EWA_VJP_CLAMPED) {
-            const float qx = pvx / pvz, qy = pvy / pvz;
-            clx = !(qx <= cam.lim_x && qx >= -cam.lim_x);
-            cly = !(qy <= cam.lim_y && qy >= -cam.lim_y);
-            ex = pvz * fminf(cam.lim_x, fmaxf(-cam.lim_x, qx));
-            ey = pvz * fminf(cam.lim_y, fmaxf(-cam.lim_y, qy));
-        }
-        const float J00 = fx * rz, J02 = -fx * ex * rz2, J11 = fy * rz, J12 = -fy * ey * rz2;
-        float T[2][3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            T[0][j] = J00 * V[j] + J02 * V[8 + j];
-            T[1][j] = J11 * V[4 + j] + J12 * V[8 + j];
-        }
-        const float c0 = cov3d[6 * i], c1 = cov3d[6 * i + 1], c2 = cov3d[6 * i + 2];
-        const float c3 = cov3d[6 * i + 3], c4 = cov3d[6 * i + 4], c5 = cov3d[6 * i + 5];
-        const float S[3][3] = {{c0, c1, c2}, {c1, c3, c4}, {c2, c4, c5}};
-        const float G[2][2] = {{vc2[0], 0.5f * vc2[1]}, {0.5f * vc2[1], vc2[2]}};
-        float GT[2][3];
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) GT[a][j] = G[a][0] * T[0][j] + G[a][1] * T[1][j];
-        float vS[3][3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int b = 0; b < 3; ++b) vS[a][b] = T[0][a] * GT[0][b] + T[1][a] * GT[1][b];
-        o_vc3[0] = vS[0][0]; o_vc3[1] = vS[0][1] + vS[1][0]; o_vc3[2] = vS[0][2] + vS[2][0];
-        o_vc3[3] = vS[1][1]; o_vc3[4] = vS[1][2] + vS[2][1]; o_vc3[5] = vS[2][2];
-        float vT[2][3];
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int j = 0; j < 3; ++j)
-                vT[a][j] = 2.f * (GT[a][0] * S[0][j] + GT[a][1] * S[1][j] + GT[a][2] * S[2][j]);
-        const float vJ00 = vT[0][0] * V[0] + vT[0][1] * V[1] + vT[0][2] * V[2];
-        const float vJ02 = vT[0][0] * V[8] + vT[0][1] * V[9] + vT[0][2] * V[10];
-        const float vJ11 = vT[1][0] * V[4] + vT[1][1] * V[5] + vT[1][2] * V[6];
-        const float vJ12 = vT[1][0] * V[8] + vT[1][1] * V[9] + vT[1][2] * V[10];
-        const float vt0 = clx ? 0.f : -fx * rz2 * vJ02, vt1 = cly ? 0.f : -fy * rz2 * vJ12;
-        // d J02 / d tz = 2 fx tx / tz^3 with tx free, fx tx / tz^3 with tx = tz * lim (clamped)
-        const float vt2 = -fx * rz2 * vJ00 + (clx ? 1.f : 2.f) * fx * ex * rz3 * vJ02 - fy * rz2 * vJ11 +
-                          (cly ? 1.f : 2.f) * fy * ey * rz3 * vJ12;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) vm[j] += V[j] * vt0 + V[4 + j] * vt1 + V[8 + j] * vt2;
-        o_vm[0] = vm[0]; o_vm[1] = vm[1]; o_vm[2] = vm[2];
-
-        const float vV[3][3] = {{o_vc3[0], 0.5f * o_vc3[1], 0.5f * o_vc3[2]},
-                                {0.5f * o_vc3[1], o_vc3[3], 0.5f * o_vc3[4]},
-                                {0.5f * o_vc3[2], 0.5f * o_vc3[4], o_vc3[5]}};
-        const float w = LG.q[0], x = LG.q[1], y = LG.q[2], z = LG.q[3];
-        float R[3][3], M[3][3], sc[3];
-        quat_to_R(w, x, y, z, R);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            sc[c] = LG.s[c];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) M[r][c] = R[r][c] * sc[c];
-        }
-        float vM[3][3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-                vM[a][c] = 2.f * (vV[a][0] * M[0][c] + vV[a][1] * M[1][c] + vV[a][2] * M[2][c]);
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-            o_vs[c] = (R[0][c] * vM[0][c] + R[1][c] * vM[1][c] + R[2][c] * vM[2][c]) * cam.glob_scale;
-        float vR[3][3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) vR[a][c] = vM[a][c] * sc[c];
-        o_vq[0] = 2.f * (x * (vR[2][1] - vR[1][2]) + y * (vR[0][2] - vR[2][0]) + z * (vR[1][0] - vR[0][1]));
-        o_vq[1] = 2.f * (-2.f * x * (vR[1][1] + vR[2][2]) + y * (vR[1][0] + vR[0][1]) +
-                         z * (vR[2][0] + vR[0][2]) + w * (vR[2][1] - vR[1][2]));
-        o_vq[2] = 2.f * (x * (vR[1][0] + vR[0][1]) - 2.f * y * (vR[0][0] + vR[2][2]) +
-                         z * (vR[2][1] + vR[1][2]) + w * (vR[0][2] - vR[2][0]));
-        o_vq[3] = 2.f * (x * (vR[2][0] + vR[0][2]) + y * (vR[2][1] + vR[1][2]) -
-                         2.f * z * (vR[0][0] + vR[1][1]) + w * (vR[1][0] - vR[0][1]));
+        project_bwd_row(i, LG, V, cam, cov3d, conics, comp, v_xy, v_depth, v_conic, v_comp, o_vm, o_vs, o_vq, o_vc2,
+                        o_vc3);
         if constexpr (FUSED != 0) {
             // chain rules of the fused front end: exp, normalisation, Hamilton product, rigid transform
 #pragma unroll
@@ -535,6 +559,80 @@ Cam bwd_cam(const float *V, float fx, float fy, float glob_scale, int semantics,
     return make_cam(V, fx, fy, 0.f, 0.f, cl ? img_h : 16, cl ? img_w : 16, 16, 0.f, glob_scale, semantics);
 }
 
+// ---- batched views (include/sgn_rast.h "Batched views") -----------------------------------------------------------------
+// One lane per Gaussian: the fused front end (raw log-scales, raw quaternions, no pose) is loaded and activated ONCE and
+// projected into every view of the table, output row b * n + i; each view's rows are what project_fwd_kernel<1> writes
+// for that camera alone (the same project_fwd_row, the same operands).
+__global__ __launch_bounds__(256) void project_views_fwd_kernel(int n, const float *__restrict__ means,
+                                                                const float *__restrict__ scales,
+                                                                const float *__restrict__ quats, Cam cam,
+                                                                const SgnViews views, float *__restrict__ cov3d,
+                                                                float *__restrict__ xys, float *__restrict__ depths,
+                                                                int32_t *__restrict__ radii, float *__restrict__ conics,
+                                                                float *__restrict__ comp,
+                                                                int32_t *__restrict__ num_tiles_hit) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const Loaded LG = load_gaussian<1>(i, means, scales, quats, cam.glob_scale, Fuse{nullptr, nullptr});
+    for (int b = 0; b < views.n; ++b) {
+        float V[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) V[k] = views.V[b][k];
+        Cam c = cam;
+        c.fx = views.fx[b]; c.fy = views.fy[b]; c.cx = views.cx[b]; c.cy = views.cy[b];
+        c.lim_x = views.lim_x[b]; c.lim_y = views.lim_y[b];
+        project_fwd_row(LG, V, c, b * n + i, cov3d, xys, depths, radii, conics, comp, num_tiles_hit);
+    }
+}
+
+// The backward: the per-view terms of the views that see the Gaussian (radii > 0) are summed in registers in ascending
+// view order, then the fused front end's chain rules (exp, normalisation) are applied once — they are linear in those
+// terms.  No atomics: every output row is written by its one lane.
+__global__ __launch_bounds__(256) void project_views_bwd_kernel(
+    int n, const float *__restrict__ means, const float *__restrict__ scales, const float *__restrict__ quats, Cam cam,
+    const SgnViews views, const float *__restrict__ cov3d, const int32_t *__restrict__ radii,
+    const float *__restrict__ conics, const float *__restrict__ comp, const float *__restrict__ v_xy,
+    const float *__restrict__ v_depth, const float *__restrict__ v_conic, const float *__restrict__ v_comp,
+    float *__restrict__ v_mean, float *__restrict__ v_scale, float *__restrict__ v_quat) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float s_vm[3] = {0.f, 0.f, 0.f}, s_vs[3] = {0.f, 0.f, 0.f}, s_vq[4] = {0.f, 0.f, 0.f, 0.f};
+    const Loaded LG = load_gaussian<1>(i, means, scales, quats, cam.glob_scale, Fuse{nullptr, nullptr});
+    bool seen = false;
+    for (int b = 0; b < views.n; ++b) {
+        const int o = b * n + i;
+        if (radii[o] <= 0) continue;
+        seen = true;
+        float V[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) V[k] = views.V[b][k];
+        Cam c = cam;
+        c.fx = views.fx[b]; c.fy = views.fy[b];
+        c.lim_x = views.lim_x[b]; c.lim_y = views.lim_y[b];
+        float vm[3], vs[3], vq[4], vc2[3], vc3[6];
+        project_bwd_row(o, LG, V, c, cov3d, conics, comp, v_xy, v_depth, v_conic, v_comp, vm, vs, vq, vc2, vc3);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { s_vm[k] += vm[k]; s_vs[k] += vs[k]; }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s_vq[k] += vq[k];
+    }
+    if (seen) {
+        // the fused front end's chain rules, as project_bwd_kernel<1> without a pose
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s_vs[c] = s_vs[c] * LG.es[c];
+        const float dq = LG.q[0] * s_vq[0] + LG.q[1] * s_vq[1] + LG.q[2] * s_vq[2] + LG.q[3] * s_vq[3];
+        float g[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) g[k] = (s_vq[k] - LG.q[k] * dq) * LG.inv_norm;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s_vq[k] = g[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { v_mean[3 * i + k] = s_vm[k]; v_scale[3 * i + k] = s_vs[k]; }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v_quat[4 * i + k] = s_vq[k];
+}
+
 }  // namespace
 
 // viewmat12 is a DEVICE pointer (the reference hands a device tensor, viewmat.squeeze()[:3,:],
@@ -648,6 +746,67 @@ SGN_EXPORT int sgn_project_bwd_fused(int n, const float *means_local, const floa
 // Pose gradient riding the fused backward: same per-Gaussian outputs as sgn_project_bwd_fused (same code, POSE adds the
 // per-wave partials after the stores), then one small pass sums the partials per object.  ws: the partials,
 // [ceil(n/64) + m, 16] floats.
+// ---- batched views: host entries (include/sgn_rast.h "Batched views")
+static int views_check(const char *fn, int n_views, int n, const sgn_view_cam *cams) {
+    if (n_views < 1 || n_views > SGN_VIEWS_MAX) {
+        sgn_set_error("%s: n_views %d outside [1, %d]", fn, n_views, SGN_VIEWS_MAX);
+        return -1;
+    }
+    if (!sgn_views_rows_ok(n_views, n)) {
+        sgn_set_error("%s: n %d: need n >= 0 and n_views * n < 2^28", fn, n);
+        return -2;
+    }
+    if (cams == nullptr) {
+        sgn_set_error("%s: cams (host table) is NULL", fn);
+        return -4;
+    }
+    return 0;
+}
+
+SGN_EXPORT int sgn_project_views_fwd(int n_views, int n, const sgn_view_cam *cams, const float *means,
+                                     const float *log_scales, float glob_scale, const float *quats_raw, int img_h,
+                                     int img_w, int block_width, float clip_thresh, float *cov3d, float *xys,
+                                     float *depths, int32_t *radii, float *conics, float *compensation,
+                                     int32_t *num_tiles_hit, int semantics, sgn_stream_t stream) {
+    if (int rc = views_check(__func__, n_views, n, cams)) return rc;
+    SGN_ARG_CHECK(img_h > 0 && img_w > 0 && block_width >= 2 && block_width <= 16, -3);
+    if (n == 0) return 0;
+    SGN_ARG_CHECK(means && log_scales && quats_raw && cov3d && xys && depths && radii && conics && compensation &&
+                      num_tiles_hit, -4);
+    const SgnViews t = sgn_views_table(n_views, cams, img_h, img_w, true);
+    const Cam cam = make_cam(nullptr, 1.f, 1.f, 0.f, 0.f, img_h, img_w, block_width, clip_thresh, glob_scale, semantics);
+    sgn_timing_begin(SGN_T_PROJECT_FWD, stream);
+    hipLaunchKernelGGL(project_views_fwd_kernel, dim3(sgn_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, n, means,
+                       log_scales, quats_raw, cam, t, cov3d, xys, depths, radii, conics, compensation, num_tiles_hit);
+    sgn_timing_end(SGN_T_PROJECT_FWD, stream);
+    SGN_LAUNCH_CHECK();
+    return 0;
+}
+
+SGN_EXPORT int sgn_project_views_bwd(int n_views, int n, const sgn_view_cam *cams, const float *means,
+                                     const float *log_scales, float glob_scale, const float *quats_raw,
+                                     const float *cov3d, const int32_t *radii, const float *conics,
+                                     const float *compensation, const float *v_xy, const float *v_depth,
+                                     const float *v_conic, const float *v_compensation, float *v_means,
+                                     float *v_log_scales, float *v_quats_raw, int semantics, int img_h, int img_w,
+                                     sgn_stream_t stream) {
+    if (int rc = views_check(__func__, n_views, n, cams)) return rc;
+    SGN_ARG_CHECK(img_h > 0 && img_w > 0, -3);
+    if (n == 0) return 0;
+    SGN_ARG_CHECK(means && log_scales && quats_raw && cov3d && radii && conics && v_xy && v_conic && v_means &&
+                      v_log_scales && v_quats_raw, -4);
+    SGN_ARG_CHECK(v_compensation == nullptr || compensation != nullptr, -5);
+    const SgnViews t = sgn_views_table(n_views, cams, img_h, img_w, (semantics & SGN_SEM_EWA_VJP_CLAMPED) != 0);
+    const Cam cam = bwd_cam(nullptr, 1.f, 1.f, glob_scale, semantics, img_h, img_w);
+    sgn_timing_begin(SGN_T_PROJECT_BWD, stream);
+    hipLaunchKernelGGL(project_views_bwd_kernel, dim3(sgn_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, n, means,
+                       log_scales, quats_raw, cam, t, cov3d, radii, conics, compensation, v_xy, v_depth, v_conic,
+                       v_compensation, v_means, v_log_scales, v_quats_raw);
+    sgn_timing_end(SGN_T_PROJECT_BWD, stream);
+    SGN_LAUNCH_CHECK();
+    return 0;
+}
+
 SGN_EXPORT size_t sgn_project_pose_workspace_bytes(int n, int m) {
     if (n < 1 || m < 1) return 0;
     return ((size_t)sgn_cdiv(n, 64) + (size_t)m + (size_t)m * POSE_BLOCKS) * 16 * sizeof(float);

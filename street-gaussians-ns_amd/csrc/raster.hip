@@ -1266,6 +1266,133 @@ __global__ __launch_bounds__(256) void unpack_grads_kernel(int n, int row0, cons
     v_opac[i] = vo;
 }
 
+// ---- batched views (include/sgn_rast.h "Batched views") -------------------------------------------------------------
+// The launch tiles of all views form one list: tile t of the binning is (view t / tiles_per_view, local tile
+// t % tiles_per_view).  The kernels below take the launch order and the two- / four-wave shapes of raster_fwd_pk_kernel /
+// raster_bwd_kernel<..., 2> / raster_bwd_short_kernel over that list and call the SAME bodies with the local tile and
+// the view's slices of bins, images, final_T / final_idx and tile statistics: pixel coordinates stay local, so every
+// view's image is what the single-view kernels produce for it.  Rows (recs, grad_ws) are indexed by global row ids.
+template <bool EXACT, bool DEPTH>
+__global__ __launch_bounds__(64) void raster_views_fwd_kernel(int W, int H, int tiles_x, int tiles_per_view,
+                                                              int n_tiles_, const int2 *__restrict__ bins,
+                                                              const Rec *__restrict__ recs,
+                                                              const int32_t *__restrict__ ids,
+                                                              const float *__restrict__ bg, float *__restrict__ out_img,
+                                                              float *__restrict__ final_T,
+                                                              int32_t *__restrict__ final_idx, int batch_thresh,
+                                                              const int32_t *__restrict__ tile_order,
+                                                              int32_t *__restrict__ tile_kmax,
+                                                              const float *__restrict__ depths,
+                                                              float *__restrict__ out_depth, int use_qm) {
+    __shared__ float4 stage[2][64 * 3];
+    __shared__ float stage_d[DEPTH ? 2 : 1][64];
+    const int n_long = min(max(tile_order[n_tiles_], 0), n_tiles_);
+    const int b_long = ((n_long + 7) >> 3) << 5;
+    const int b = (int)blockIdx.x;
+    int t_idx, wv;
+    const bool is_long = b < b_long;
+    if (is_long) {
+        t_idx = (b >> 5) * 8 + (b & 7);
+        wv = (b >> 3) & 3;
+        if (t_idx >= n_long) return;
+    } else {
+        const int b2 = b - b_long;
+        t_idx = n_long + (b2 >> 4) * 8 + (b2 & 7);
+        wv = (b2 >> 3) & 1;
+        if (t_idx >= n_tiles_) return;
+    }
+    const int tile = tile_order[t_idx];
+    const int view = tile / tiles_per_view, lt = tile - view * tiles_per_view;
+    const size_t px0 = (size_t)view * W * H;
+    const FwdGroups G = {};
+    raster_fwd_pk_body<EXACT, DEPTH, false>(lt, wv, is_long, W, H, tiles_x, tiles_per_view,
+                                            bins + (size_t)view * tiles_per_view, recs, ids, bg, out_img + 3 * px0,
+                                            final_T + px0, final_idx + px0, batch_thresh,
+                                            tile_kmax + 2 * (size_t)view * tiles_per_view, depths,
+                                            DEPTH ? out_depth + px0 : out_depth, use_qm, G, stage, stage_d);
+}
+
+// long reverse walks: four lean waves per tile (raster_bwd_kernel MODE 2)
+template <bool EXACT, int REDUCE>
+__global__ __launch_bounds__(64) void raster_views_bwd_kernel(int W, int H, int tiles_x, int tiles_per_view,
+                                                              int n_tiles, const int2 *__restrict__ bins,
+                                                              const Rec *__restrict__ recs,
+                                                              const int32_t *__restrict__ ids,
+                                                              const float *__restrict__ bg,
+                                                              const float *__restrict__ final_T,
+                                                              const int32_t *__restrict__ final_idx,
+                                                              const float *__restrict__ v_out,
+                                                              const float *__restrict__ v_out_alpha, float alpha_clamp,
+                                                              float *__restrict__ grad_ws, int dbg, int adapt_thresh,
+                                                              int batch_thresh, const int32_t *__restrict__ tile_order,
+                                                              int use_qm) {
+    if ((int)blockIdx.x >= 4 * tile_order[n_tiles]) return;
+    __builtin_amdgcn_s_setprio(3);
+    const int tile = tile_order[blockIdx.x >> 2];
+    const int view = tile / tiles_per_view, lt = tile - view * tiles_per_view;
+    const size_t px0 = (size_t)view * W * H;
+    raster_bwd_tile<EXACT, REDUCE, 1, false>(lt, blockIdx.x & 3, W, H, 16, tiles_x,
+                                             bins + (size_t)view * tiles_per_view, recs, ids, bg, final_T + px0,
+                                             final_idx + px0, v_out ? v_out + 3 * px0 : v_out, v_out_alpha + px0,
+                                             alpha_clamp, grad_ws, dbg, adapt_thresh, batch_thresh, use_qm);
+}
+
+// the other walks: one wave per tile, held at four waves per SIMD like raster_bwd_short_kernel
+template <bool EXACT, int REDUCE>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, SGN_BWD_SHORT_WAVES_MAX))) void
+raster_views_bwd_short_kernel(int W, int H, int tiles_x, int tiles_per_view, int n_tiles,
+                              const int2 *__restrict__ bins, const Rec *__restrict__ recs,
+                              const int32_t *__restrict__ ids, const float *__restrict__ bg,
+                              const float *__restrict__ final_T, const int32_t *__restrict__ final_idx,
+                              const float *__restrict__ v_out, const float *__restrict__ v_out_alpha, float alpha_clamp,
+                              float *__restrict__ grad_ws, int dbg, int adapt_thresh, int batch_thresh,
+                              const int32_t *__restrict__ tile_order, int use_qm) {
+    const int n_long = tile_order[n_tiles];
+    if ((int)blockIdx.x < n_long) return;
+    const int tile = tile_order[blockIdx.x];
+    const int view = tile / tiles_per_view, lt = tile - view * tiles_per_view;
+    const size_t px0 = (size_t)view * W * H;
+    raster_bwd_tile<EXACT, REDUCE, 4, false>(lt, 0, W, H, 16, tiles_x, bins + (size_t)view * tiles_per_view, recs,
+                                             ids, bg, final_T + px0, final_idx + px0,
+                                             v_out ? v_out + 3 * px0 : v_out, v_out_alpha + px0, alpha_clamp, grad_ws,
+                                             dbg, adapt_thresh, batch_thresh, use_qm);
+}
+
+// opacity logits [n] -> the per-row copy [n_views * n] the binning's culling and the row build read
+__global__ __launch_bounds__(256) void views_repeat_kernel(int n, int n_views, const float *__restrict__ src,
+                                                           float *__restrict__ dst) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float v = src[i];
+    for (int b = 0; b < n_views; ++b) dst[(size_t)b * n + i] = v;
+}
+
+// unpack_grads_kernel for every row of every view (opacity logits), with d/d logit summed over the n_views rows of
+// each Gaussian in ascending view order: v_opac [n]
+__global__ __launch_bounds__(256) void unpack_views_kernel(int n, int n_views, const float *__restrict__ ws,
+                                                           const float *__restrict__ conics,
+                                                           const float *__restrict__ logits, float *__restrict__ v_xy,
+                                                           float *__restrict__ v_conic, float *__restrict__ v_colors,
+                                                           float *__restrict__ v_opac) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float sg = 1.f / (1.f + expf(-logits[i]));
+    float vsum = 0.f;
+    for (int v = 0; v < n_views; ++v) {
+        const size_t r = (size_t)v * n + i;
+        const float4 a = reinterpret_cast<const float4 *>(ws)[3 * r + 0];
+        const float4 b = reinterpret_cast<const float4 *>(ws)[3 * r + 1];
+        const float4 c = reinterpret_cast<const float4 *>(ws)[3 * r + 2];
+        const float A = conics[3 * r], B = conics[3 * r + 1], C = conics[3 * r + 2];
+        v_xy[2 * r] = fmaf(A, a.x, B * a.y);
+        v_xy[2 * r + 1] = fmaf(B, a.x, C * a.y);
+        v_conic[3 * r] = 0.5f * a.z; v_conic[3 * r + 1] = a.w; v_conic[3 * r + 2] = 0.5f * b.x;
+        v_colors[3 * r] = b.y; v_colors[3 * r + 1] = b.z; v_colors[3 * r + 2] = b.w;
+        vsum += c.x * sg * (1.f - sg);
+    }
+    v_opac[i] = vsum;
+}
+
 // Kernel-selection options arrive with every call (include/sgn_rast.h: sgn_raster_opts); NULL = defaults.
 sgn_raster_opts resolve_opts(const sgn_raster_opts *o) {
     sgn_raster_opts r;
@@ -1653,4 +1780,90 @@ SGN_EXPORT int sgn_raster_bwd_part(int img_h, int img_w, int block_width, int n,
                                    int first, int last) {
     SGN_ARG_CHECK(!window, -13);
     return raster_bwd_impl(img_h, img_w, block_width, n, n_isect, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, opacity_is_logit, id_lo, id_hi, window, background3, final_Ts, final_idx, v_out_img, v_out_alpha, alpha_clamp_bwd, v_xy, v_conic, v_colors, v_opacity, recs_ws, recs_ws_bytes, recs_packed, grad_ws, grad_ws_bytes, tile_order, colors_pre_clamp, opts, stream, aux_stream, first ? 0 : 1, last ? 0 : 1);
+}
+
+
+// ---- batched views: host side of the raster passes (api.cpp sgn_rasterize_views_*_all)
+int sgn_views_repeat(int n, int n_views, const float *src, float *dst, sgn_stream_t stream) {
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(views_repeat_kernel, dim3(sgn_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, n, n_views, src,
+                       dst);
+    SGN_LAUNCH_CHECK();
+    return 0;
+}
+
+// forward kernels over the n_views * tiles tiles of an emitted list (tile_order from sgn_tile_order over all of them;
+// tile_kmax cleared by the emission); rows built (sgn_raster_build_rows over n_views * n rows)
+int sgn_raster_views_fwd(int n_views, int img_h, int img_w, const int32_t *ids, const int32_t *tile_bins,
+                         const void *rows, const float *background3, float *out_img, float *final_Ts,
+                         int32_t *final_idx, const int32_t *tile_order, int32_t *tile_kmax, const float *depths,
+                         float *out_depth, const sgn_raster_opts *opts, sgn_stream_t stream) {
+    const sgn_raster_opts o = resolve_opts(opts);
+    const int tiles_x = (img_w + 15) / 16, tiles_y = (img_h + 15) / 16, tpv = tiles_x * tiles_y;
+    const int n_tiles = tpv * n_views;
+    hipStream_t s = (hipStream_t)stream;
+    sgn_timing_begin(SGN_T_RASTER_FWD, s);
+#define SGN_LAUNCH_VFWD(EX, DE)                                                                                      \
+    hipLaunchKernelGGL((raster_views_fwd_kernel<EX, DE>), dim3(((n_tiles + 7) / 8) * 32 + 32), dim3(64), 0, s, img_w,   \
+                       img_h, tiles_x, tpv, n_tiles, (const int2 *)tile_bins, (const Rec *)rows, ids, background3,      \
+                       out_img, final_Ts, final_idx, o.batch_fwd, tile_order, tile_kmax, depths, out_depth, o.ids_qmask)
+    if (o.exact_exp) {
+        if (depths) SGN_LAUNCH_VFWD(true, true); else SGN_LAUNCH_VFWD(true, false);
+    } else {
+        if (depths) SGN_LAUNCH_VFWD(false, true); else SGN_LAUNCH_VFWD(false, false);
+    }
+#undef SGN_LAUNCH_VFWD
+    sgn_timing_end(SGN_T_RASTER_FWD, s);
+    SGN_LAUNCH_CHECK();
+    return 0;
+}
+
+// backward: reverse walks (tile_order from sgn_tile_order with the forward's statistics) into grad_ws, then the unpack
+int sgn_raster_views_bwd(int n_views, int n, int img_h, int img_w, const int32_t *ids, const int32_t *tile_bins,
+                         const void *rows, const float *conics, const float *logits, const float *background3,
+                         const float *final_Ts, const int32_t *final_idx, const float *v_out_img,
+                         const float *v_out_alpha, float alpha_clamp_bwd, float *v_xy, float *v_conic, float *v_colors,
+                         float *v_opacity, void *grad_ws, const int32_t *tile_order, const sgn_raster_opts *opts,
+                         sgn_stream_t stream, sgn_stream_t aux_stream) {
+    const sgn_raster_opts o = resolve_opts(opts);
+    const int tiles_x = (img_w + 15) / 16, tiles_y = (img_h + 15) / 16, tpv = tiles_x * tiles_y;
+    const int n_tiles = tpv * n_views;
+    const int rows_n = n_views * n;
+    hipStream_t s = (hipStream_t)stream;
+    SGN_HIP_CHECK(hipMemsetAsync(grad_ws, 0, (size_t)rows_n * SGN_RECORD_FLOATS * sizeof(float), s));
+    hipStream_t s2 = s;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    if (aux_stream != nullptr && (hipStream_t)aux_stream != s && sgn_fork_events(&ev_fork, &ev_join) == 0) {
+        s2 = (hipStream_t)aux_stream;
+        SGN_HIP_CHECK(hipEventRecord(ev_fork, s));
+        SGN_HIP_CHECK(hipStreamWaitEvent(s2, ev_fork, 0));
+    }
+    sgn_timing_begin(SGN_T_RASTER_BWD, s);
+#define SGN_VBWD_ARGS                                                                                            \
+    img_w, img_h, tiles_x, tpv, n_tiles, (const int2 *)tile_bins, (const Rec *)rows, ids, background3, final_Ts,  \
+        final_idx, v_out_img, v_out_alpha, alpha_clamp_bwd, (float *)grad_ws, o.debug_flags, o.adapt_bwd,         \
+        o.batch_bwd, tile_order, o.ids_qmask
+#define SGN_LAUNCH_VBWD(EX, RM)                                                                                  \
+    do {                                                                                                         \
+        hipLaunchKernelGGL((raster_views_bwd_kernel<EX, RM>), dim3(n_tiles * 4), dim3(64), 0, s2, SGN_VBWD_ARGS); \
+        hipLaunchKernelGGL((raster_views_bwd_short_kernel<EX, RM>), dim3(n_tiles), dim3(64), 0, s, SGN_VBWD_ARGS); \
+    } while (0)
+    if (o.exact_exp) {
+        if (o.reduce_mode) SGN_LAUNCH_VBWD(true, 1); else SGN_LAUNCH_VBWD(true, 0);
+    } else {
+        if (o.reduce_mode) SGN_LAUNCH_VBWD(false, 1); else SGN_LAUNCH_VBWD(false, 0);
+    }
+#undef SGN_LAUNCH_VBWD
+#undef SGN_VBWD_ARGS
+    if (s2 != s) {
+        SGN_HIP_CHECK(hipEventRecord(ev_join, s2));
+        SGN_HIP_CHECK(hipStreamWaitEvent(s, ev_join, 0));
+    }
+    sgn_timing_end(SGN_T_RASTER_BWD, s);
+    sgn_timing_begin(SGN_T_UNPACK, s);
+    hipLaunchKernelGGL(unpack_views_kernel, dim3(sgn_cdiv(n, 256)), dim3(256), 0, s, n, n_views, (const float *)grad_ws,
+                       conics, logits, v_xy, v_conic, v_colors, v_opacity);
+    sgn_timing_end(SGN_T_UNPACK, s);
+    SGN_LAUNCH_CHECK();
+    return 0;
 }

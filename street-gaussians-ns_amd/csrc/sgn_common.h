@@ -49,6 +49,36 @@ int sgn_project_fwd_checked(int n, const float *means3d, const float *scales, fl
                             float *conics, float *compensation, int32_t *num_tiles_hit, int32_t *quat_flag,
                             float quat_tol, int32_t quat_stamp, int32_t *quat_ok, int semantics, sgn_stream_t stream);
 
+// Batched views (include/sgn_rast.h "Batched views"): the camera table travels BY VALUE as a kernel argument (SGPRs /
+// the kernarg segment, no device buffer, no copy), one entry per view; the host fills it from sgn_view_cam rows.
+struct SgnViews {
+    int n;                                  // views, 1..SGN_VIEWS_MAX
+    float V[SGN_VIEWS_MAX][12];             // world -> camera, 3x4 row-major
+    float fx[SGN_VIEWS_MAX], fy[SGN_VIEWS_MAX], cx[SGN_VIEWS_MAX], cy[SGN_VIEWS_MAX];
+    float lim_x[SGN_VIEWS_MAX], lim_y[SGN_VIEWS_MAX];   // 1.3 tan(fov / 2) of the projection's clamp
+    float pos[SGN_VIEWS_MAX][3];            // camera centre (SH view directions)
+};
+// argument checks shared by the batched entries: 1 <= n_views <= SGN_VIEWS_MAX, n >= 0 and n_views * n < 2^28 (sorted
+// ids carry quadrant masks in bits 28-31)
+static inline bool sgn_views_rows_ok(int n_views, int n) {
+    return n >= 0 && (int64_t)n_views * (int64_t)n < ((int64_t)1 << 28);
+}
+static inline SgnViews sgn_views_table(int n_views, const sgn_view_cam *cams, int img_h, int img_w, bool lim_from_image) {
+    SgnViews t = {};
+    t.n = n_views;
+    for (int b = 0; b < n_views; ++b) {
+        const sgn_view_cam &c = cams[b];
+        for (int k = 0; k < 12; ++k) t.V[b][k] = c.viewmat[k];
+        t.fx[b] = c.fx; t.fy[b] = c.fy; t.cx[b] = c.cx; t.cy[b] = c.cy;
+        // as project.hip make_cam / bwd_cam: the backward needs the image's clamp only for SGN_SEM_EWA_VJP_CLAMPED
+        const int w = lim_from_image ? img_w : 16, h = lim_from_image ? img_h : 16;
+        t.lim_x[b] = 1.3f * (0.5f * (float)w / c.fx);
+        t.lim_y[b] = 1.3f * (0.5f * (float)h / c.fy);
+        for (int k = 0; k < 3; ++k) t.pos[b][k] = c.cam_pos[k];
+    }
+    return t;
+}
+
 static inline int sgn_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 // float -> int with v_cvt_i32_f32 semantics (saturating, NaN -> 0); the C oracle spells the

@@ -883,3 +883,165 @@ SGN_EXPORT int sgn_sh_bwd_parts(int n_parts, const int32_t *rows_host, const int
     SGN_LAUNCH_CHECK();
     return 0;
 }
+
+// ---- batched views (include/sgn_rast.h "Batched views") -----------------------------------------------------------------
+// The fused SH front end for B cameras at once: a wave stages its 64 rows of features_rest into LDS ONCE and every lane
+// evaluates its Gaussian from each camera of the table, colour row b * n + i.  Per view the arithmetic is
+// sh_fwd_fused_kernel's with n_fourier = 1 and idft = {1} (dc_eff = 0 + dc * 1), operation by operation.  The backward
+// sums the views' coefficient gradients in registers in ascending view order (as sh_bwd_multi_kernel, plus the
+// clamp's mask of the fused backward) and writes each coefficient once: no atomics.
+namespace {
+
+template <int K, int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void sh_views_fwd_kernel(int n, int deg, const SgnViews views,
+                                                                  const float *__restrict__ means,
+                                                                  const float *__restrict__ dc,
+                                                                  const float *__restrict__ rest, int post,
+                                                                  float *__restrict__ colors) {
+    constexpr int KC = (K - 1) * 3, LS = (KC | 1);
+    __shared__ float lds[WAVES][64 * (KC > 0 ? LS : 1)];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int g0 = (blockIdx.x * WAVES + wave) * 64;
+    const int cnt = max(0, min(64, n - g0));
+    float *my = lds[wave];
+    if constexpr (KC > 0) stage_rows<KC, LS>(my, rest + (size_t)g0 * KC, cnt, lane);
+    __syncthreads();
+    if (lane >= cnt) return;
+    const int i = g0 + lane;
+    const float m0 = means[3 * i], m1 = means[3 * i + 1], m2 = means[3 * i + 2];
+    const float wf = 1.f;
+    const float d0 = 0.f + dc[3 * i] * wf, d1 = 0.f + dc[3 * i + 1] * wf, d2 = 0.f + dc[3 * i + 2] * wf;
+    for (int v = 0; v < views.n; ++v) {
+        float b[25];
+        const int nb = sh_bases(m0 - views.pos[v][0], m1 - views.pos[v][1], m2 - views.pos[v][2], deg, b);
+        float a0 = b[0] * d0, a1 = b[0] * d1, a2 = b[0] * d2;
+        if constexpr (KC > 0) {
+            const float *row = my + lane * LS;
+#pragma unroll
+            for (int k = 1; k < K; ++k) {
+                if (k < nb) {
+                    a0 += b[k] * row[3 * (k - 1)];
+                    a1 += b[k] * row[3 * (k - 1) + 1];
+                    a2 += b[k] * row[3 * (k - 1) + 2];
+                }
+            }
+        }
+        if (post) { a0 = fmaxf(a0 + 0.5f, 0.f); a1 = fmaxf(a1 + 0.5f, 0.f); a2 = fmaxf(a2 + 0.5f, 0.f); }
+        const size_t o = (size_t)v * n + i;
+        colors[3 * o] = a0; colors[3 * o + 1] = a1; colors[3 * o + 2] = a2;
+    }
+}
+
+template <int K, int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void sh_views_bwd_kernel(int n, int deg, const SgnViews views,
+                                                                  const float *__restrict__ means, int post,
+                                                                  const float *__restrict__ colors,
+                                                                  const float *__restrict__ v_colors,
+                                                                  float *__restrict__ v_dc, float *__restrict__ v_rest) {
+    constexpr int KC = K * 3, LS = (KC | 1);
+    __shared__ float lds[WAVES][64 * LS];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int g0 = (blockIdx.x * WAVES + wave) * 64;
+    const int cnt = max(0, min(64, n - g0));
+    float *my = lds[wave];
+    if (lane < cnt) {
+        const int i = g0 + lane;
+        const float m0 = means[3 * i], m1 = means[3 * i + 1], m2 = means[3 * i + 2];
+        float acc[KC];
+#pragma unroll
+        for (int e = 0; e < KC; ++e) acc[e] = 0.f;
+        for (int v = 0; v < views.n; ++v) {
+            const size_t o = (size_t)v * n + i;
+            float v0 = v_colors[3 * o], v1 = v_colors[3 * o + 1], v2 = v_colors[3 * o + 2];
+            if (post) {  // clamp(x + 0.5, min=0): gradient passes where the output is positive
+                v0 = colors[3 * o] > 0.f ? v0 : 0.f;
+                v1 = colors[3 * o + 1] > 0.f ? v1 : 0.f;
+                v2 = colors[3 * o + 2] > 0.f ? v2 : 0.f;
+            }
+            float b[25];
+            const int nb = sh_bases(m0 - views.pos[v][0], m1 - views.pos[v][1], m2 - views.pos[v][2], deg, b);
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const float bk = (k < nb) ? b[k] : 0.f;
+                acc[3 * k] += bk * v0; acc[3 * k + 1] += bk * v1; acc[3 * k + 2] += bk * v2;
+            }
+        }
+        float *row = my + lane * LS;
+#pragma unroll
+        for (int e = 0; e < KC; ++e) row[e] = acc[e];
+    }
+    __syncthreads();
+    for (int e = lane; e < cnt * 3; e += 64) v_dc[(size_t)g0 * 3 + e] = my[(e / 3) * LS + (e % 3)];
+    if constexpr (KC > 3) {
+        constexpr int RC = KC - 3;
+        float *dst = v_rest + (size_t)g0 * RC;
+        for (int e = lane; e < cnt * RC; e += 64) {
+            const int r = e / RC, c = e - r * RC;
+            dst[e] = my[r * LS + 3 + c];
+        }
+    }
+}
+
+template <int K>
+void launch_views(bool fwd, int n, int deg, const SgnViews &t, const float *means, const float *dc, const float *rest,
+                  int post, const float *colors, const float *v_colors, float *out_colors, float *v_dc, float *v_rest,
+                  hipStream_t s) {
+    constexpr int WAVES = (K > 16) ? 2 : 4;
+    if (fwd)
+        hipLaunchKernelGGL((sh_views_fwd_kernel<K, WAVES>), dim3(sgn_cdiv(n, WAVES * 64)), dim3(WAVES * 64), 0, s, n,
+                           deg, t, means, dc, rest, post, out_colors);
+    else
+        hipLaunchKernelGGL((sh_views_bwd_kernel<K, WAVES>), dim3(sgn_cdiv(n, WAVES * 64)), dim3(WAVES * 64), 0, s, n,
+                           deg, t, means, post, colors, v_colors, v_dc, v_rest);
+}
+
+int sh_views(const char *fn, bool fwd, int n_views, int n, int k, int degree, const sgn_view_cam *cams,
+             const float *means, const float *dc, const float *rest, int post, const float *colors,
+             const float *v_colors, float *out_colors, float *v_dc, float *v_rest, hipStream_t s) {
+    if (n_views < 1 || n_views > SGN_VIEWS_MAX) {
+        sgn_set_error("%s: n_views %d outside [1, %d]", fn, n_views, SGN_VIEWS_MAX);
+        return -1;
+    }
+    if (!sgn_views_rows_ok(n_views, n)) {
+        sgn_set_error("%s: n %d: need n >= 0 and n_views * n < 2^28", fn, n);
+        return -2;
+    }
+    if (!(k == 1 || k == 4 || k == 9 || k == 16 || k == 25) || degree < 0 || (degree + 1) * (degree + 1) > k) {
+        sgn_set_error("%s: k %d / degree %d", fn, k, degree);
+        return -3;
+    }
+    if (!cams || (n > 0 && (!means || (fwd ? (!dc || !out_colors || (k > 1 && !rest))
+                                           : (!colors || !v_colors || !v_dc || (k > 1 && !v_rest)))))) {
+        sgn_set_error("%s: a required pointer is NULL", fn);
+        return -4;
+    }
+    if (n == 0) return 0;
+    const SgnViews t = sgn_views_table(n_views, cams, 16, 16, false);
+    sgn_timing_begin(fwd ? SGN_T_SH_FWD : SGN_T_SH_BWD, s);
+    switch (k) {
+        case 1: launch_views<1>(fwd, n, degree, t, means, dc, rest, post, colors, v_colors, out_colors, v_dc, v_rest, s); break;
+        case 4: launch_views<4>(fwd, n, degree, t, means, dc, rest, post, colors, v_colors, out_colors, v_dc, v_rest, s); break;
+        case 9: launch_views<9>(fwd, n, degree, t, means, dc, rest, post, colors, v_colors, out_colors, v_dc, v_rest, s); break;
+        case 16: launch_views<16>(fwd, n, degree, t, means, dc, rest, post, colors, v_colors, out_colors, v_dc, v_rest, s); break;
+        default: launch_views<25>(fwd, n, degree, t, means, dc, rest, post, colors, v_colors, out_colors, v_dc, v_rest, s); break;
+    }
+    sgn_timing_end(fwd ? SGN_T_SH_FWD : SGN_T_SH_BWD, s);
+    SGN_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace
+
+SGN_EXPORT int sgn_sh_views_fwd(int n_views, int n, int k, int degree, const sgn_view_cam *cams, const float *means,
+                                const float *features_dc, const float *features_rest, int post_half_clamp,
+                                float *colors, sgn_stream_t stream) {
+    return sh_views(__func__, true, n_views, n, k, degree, cams, means, features_dc, features_rest, post_half_clamp,
+                    nullptr, nullptr, colors, nullptr, nullptr, (hipStream_t)stream);
+}
+
+SGN_EXPORT int sgn_sh_views_bwd(int n_views, int n, int k, int degree, const sgn_view_cam *cams, const float *means,
+                                int post_half_clamp, const float *colors, const float *v_colors, float *v_features_dc,
+                                float *v_features_rest, sgn_stream_t stream) {
+    return sh_views(__func__, false, n_views, n, k, degree, cams, means, nullptr, nullptr, post_half_clamp, colors,
+                    v_colors, nullptr, v_features_dc, v_features_rest, (hipStream_t)stream);
+}

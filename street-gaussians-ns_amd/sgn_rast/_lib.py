@@ -113,6 +113,18 @@ SIGNATURES = {
                             _f, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "sgn_raster_bwd_part": (_i, [_i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
                                  _vp, _f, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i, _i]),
+    "sgn_project_views_fwd": (_i, [_i, _i, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i,
+                                   _vp]),
+    "sgn_project_views_bwd": (_i, [_i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _i, _i, _i, _vp]),
+    "sgn_sh_views_fwd": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "sgn_sh_views_bwd": (_i, [_i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sgn_rasterize_views_arena_bytes": (_sz, [_i, _i, _i64]),
+    "sgn_rasterize_views_fwd_all": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp,
+                                         _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _i, _i, _vp,
+                                         _vp]),
+    "sgn_rasterize_views_bwd_all": (_i, [_i, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp,
+                                         _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _i, _vp, _vp, _vp]),
     "sgn_knn_workspace_bytes": (_sz, [_i, _i]),
     "sgn_knn": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
@@ -129,6 +141,15 @@ class RasterOpts(C.Structure):
         out = RasterOpts()
         C.memmove(C.byref(out), C.byref(self), C.sizeof(RasterOpts))
         return out
+
+
+VIEWS_MAX = 16      # SGN_VIEWS_MAX
+
+
+class ViewCam(C.Structure):
+    """`sgn_view_cam` of include/sgn_rast.h: one camera of a batched-views call (a host array of these is passed)."""
+    _fields_ = [("viewmat", C.c_float * 12), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("cam_pos", C.c_float * 3)]
 
 
 # The library itself is stateless; the HOST keeps the options: one process-wide default object (library defaults,
