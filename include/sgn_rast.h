@@ -692,6 +692,26 @@ int sgn_l1_ssim_fwd(int h, int w, const float *pred, const float *gt, float data
 int sgn_l1_ssim_bwd(int h, int w, const float *pred, const float *gt, float clamp_max, const void *ws,
                     const float *gscale2, float *v_pred, sgn_stream_t stream);
 
+/* The same loss under the batch's pixel mask (sgn_splatfacto.py:1081-1087 in training, :1135-1151 in evaluation:
+ * `gt_img *= mask; rgb *= mask` in front of the two terms), plus the mean squared error that PSNR needs.  mask: h*w
+ * DEVICE bytes, non-zero = keep; NULL = no mask (the fourth output is still produced).  The kernels work on
+ * min(pred, clamp_max) * m and gt * m; neither image is modified.  The reference's semantics, not the obvious ones:
+ *   - both means keep their unmasked denominators, 3 h w for Ll1 (and the mse) and 3 (h-10) (w-10) for ssim: the
+ *     reference multiplies and then calls .mean(); nothing is normalised by the number of kept pixels;
+ *   - an SSIM window that straddles the mask edge sees zeros on both images; it is neither skipped nor reweighted;
+ *   - the clamp is applied before the mask (:969 before :1083).
+ * out4 (device, 4 floats) = Ll1, ssim, (1 - ssim_lambda) Ll1 + ssim_lambda (1 - ssim), mse = mean (gt m - pred m)^2.
+ * ws >= sgn_l1_ssim_masked_workspace_bytes (its layout is NOT the unmasked entries': pass it to the masked backward
+ * only).  The backward writes v_pred = m [pred <= clamp_max] (the unmasked expression on the masked images): an
+ * exact 0 where m = 0.  Return codes: -1 h or w <= 10, -2 a NULL pred / gt / out4 / ws (backward: gscale2, v_pred),
+ * -3 ws_bytes too small; all before anything is launched. */
+size_t sgn_l1_ssim_masked_workspace_bytes(int h, int w, int with_grad);
+int sgn_l1_ssim_masked_fwd(int h, int w, const float *pred, const float *gt, const unsigned char *mask,
+                           float data_range, float clamp_max, float ssim_lambda, float *out4, int with_grad, void *ws,
+                           size_t ws_bytes, sgn_stream_t stream);
+int sgn_l1_ssim_masked_bwd(int h, int w, const float *pred, const float *gt, const unsigned char *mask,
+                           float clamp_max, const void *ws, const float *gscale2, float *v_pred, sgn_stream_t stream);
+
 /* Accumulation regularisers of the reference's loss dictionary, means over the n_pixels = H*W
  * entries of [H,W,1] accumulation images, one pass each way for both terms (either may be absent):
  *   out2[0] = mean([semantic == sky_value] * accumulation)      sgn_splatfacto.py:1090-1093 (losses["sky_accumulation"]

@@ -14,6 +14,11 @@
 //   backward: 26x26 patch of those three maps -> LDS, same separable filter (transposed valid correlation:
 //             zero outside the valid domain), grad = G*A + 2x G*B + y G*C, fused with the L1 sign term.
 // HBM-bound by design: forward reads 2 images and writes 3 maps, backward reads 3 maps + 2 images and writes 1.
+//
+// Masked forms (the batch's boolean `mask`, sgn_splatfacto.py:1081-1087 and :1135-1151: `gt_img *= mask; rgb *= mask`
+// in front of the same two terms): template instantiations of the same kernels that read one mask byte per pixel and
+// work on min(pred, clamp_max) * m and gt * m.  The unmasked instantiations compile to the code they had before the
+// mask existed.  The masked entry points also sum (gt m - pred m)^2 per workgroup: the MSE that PSNR needs.
 #include "sgn_common.h"
 
 namespace {
@@ -37,11 +42,17 @@ constexpr int ROWS_ = ROWF + 3;       // LDS row stride (odd: 3q + c walks disti
 
 // pred/gt [H,W,3]; per-workgroup partial sums of |gt - pred| (all pixels) and of ssim_map (valid region);
 // dmaps [3 maps][3 channels][H-10][W-10]: dS/d mu_pred, dS/d E[pred^2], dS/d E[pred*gt] (NULL: no backward wanted)
+// MASKED: mask [H,W] bytes, non-zero = keep; the patch holds min(pred, cmax) * m and gt * m (clamp first, then mask, as
+//         the reference does), so L1 and every SSIM window — also one that straddles the mask edge — see zeros on both
+//         images where m = 0.  The means keep their unmasked denominators (the reference multiplies, then .mean()).
+// MSE:    a third partial per workgroup, the sum of (gt m - pred m)^2 over the tile (partials stride 3 instead of 2).
+template <bool MASKED, bool MSE>
 __global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(int H, int W, Win win, float C1, float C2, float cmax,
                                                           const float *__restrict__ pred,
                                                           const float *__restrict__ gt,
                                                           float *__restrict__ partials,
-                                                          float *__restrict__ dmaps) {
+                                                          float *__restrict__ dmaps,
+                                                          const unsigned char *__restrict__ mask) {
     __shared__ float px[PS][ROWS_], py[PS][ROWS_];            // HWC patch, all three channels: contiguous row loads
     __shared__ float hm[5][PS][TS + 1];
     __shared__ float lds4[4];
@@ -55,6 +66,7 @@ __global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(int H, int W, Win win,
         // trip per iteration: s_waitcnt vmcnt(0) after every global_load)
         constexpr int NL = (PS * ROWF + 255) / 256;
         float va[NL], vb[NL];
+        [[maybe_unused]] unsigned char vm[MASKED ? NL : 1];
 #pragma unroll
         for (int it = 0; it < NL; ++it) {
             const int e = tid + it * 256;
@@ -64,6 +76,16 @@ __global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(int H, int W, Win win,
             const size_t idx = (size_t)iy * rowlen + gx;
             va[it] = ok ? fminf(pred[idx], cmax) : 0.f;      // fused torch.clamp(rgb, max=1) (sgn_splatfacto.py:969)
             vb[it] = ok ? gt[idx] : 0.f;
+            if constexpr (MASKED)                            // ok: gx < 3W, so the pixel column x0 + j / 3 < W
+                vm[it] = ok ? mask[(size_t)iy * W + x0 + j / 3] : (unsigned char)0;
+        }
+        if constexpr (MASKED) {
+#pragma unroll
+            for (int it = 0; it < NL; ++it) {                 // `* 1.0f` is exact: an all-ones mask changes no bit
+                const float m = vm[it] ? 1.f : 0.f;
+                va[it] *= m;
+                vb[it] *= m;
+            }
         }
 #pragma unroll
         for (int it = 0; it < NL; ++it) {
@@ -76,10 +98,14 @@ __global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(int H, int W, Win win,
         }
     }
     __syncthreads();
-    float l1 = 0.f, ss = 0.f;
+    float l1 = 0.f, ss = 0.f, sq = 0.f;
     if (in_img) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) l1 += fabsf(py[ty][tx * 3 + c] - px[ty][tx * 3 + c]);
+        for (int c = 0; c < 3; ++c) {
+            const float d = py[ty][tx * 3 + c] - px[ty][tx * 3 + c];
+            l1 += fabsf(d);
+            if constexpr (MSE) sq += d * d;
+        }
     }
     const size_t plane = (size_t)Ho * Wo;
     for (int c = 0; c < 3; ++c) {
@@ -129,39 +155,55 @@ __global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(int H, int W, Win win,
     }
     const float bl1 = block_sum(l1, lds4);
     const float bss = block_sum(ss, lds4);
+    float bsq = 0.f;
+    if constexpr (MSE) bsq = block_sum(sq, lds4);
     if (tid == 0) {   // one slot per workgroup: 9600 same-address float atomics cost more than the whole kernel
+        constexpr int NP = MSE ? 3 : 2;
         const size_t b = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-        partials[2 * b] = bl1;
-        partials[2 * b + 1] = bss;
+        partials[NP * b] = bl1;
+        partials[NP * b + 1] = bss;
+        if constexpr (MSE) partials[NP * b + 2] = bsq;
     }
 }
 
 // out3 = [Ll1 = mean |gt - pred|, ssim mean, (1 - lambda) Ll1 + lambda (1 - ssim)]: the means and the reference's
 // weighted sum (sgn_splatfacto.py:1086-1087) come out of the reduction itself instead of a dozen scalar torch kernels
+// MSE (the masked entry points): partials have stride 3 and out3 a fourth slot, the mean squared error over 3HW
+template <bool MSE>
 __global__ __launch_bounds__(256) void l1_ssim_reduce_kernel(int nblk, const float *__restrict__ partials,
                                                              float inv_n_l1, float inv_n_ss, float lambda,
                                                              float *__restrict__ out3) {
     __shared__ float lds4[4];
-    float a = 0.f, b = 0.f;
-    for (int i = threadIdx.x; i < nblk; i += 256) { a += partials[2 * i]; b += partials[2 * i + 1]; }
+    constexpr int NP = MSE ? 3 : 2;
+    float a = 0.f, b = 0.f, q = 0.f;
+    for (int i = threadIdx.x; i < nblk; i += 256) {
+        a += partials[NP * i]; b += partials[NP * i + 1];
+        if constexpr (MSE) q += partials[NP * i + 2];
+    }
     a = block_sum(a, lds4);
     b = block_sum(b, lds4);
+    if constexpr (MSE) q = block_sum(q, lds4);
     if (threadIdx.x == 0) {
         const float l1 = a * inv_n_l1, ss = b * inv_n_ss;
         out3[0] = l1;
         out3[1] = ss;
         out3[2] = (1.f - lambda) * l1 + lambda * (1.f - ss);
+        if constexpr (MSE) out3[3] = q * inv_n_l1;
     }
 }
 
 // v_pred [H,W,3] = gl1 * sign(pred - gt) / (3HW) + gss / (3 Ho Wo) * (G*A + 2 pred G*B + gt G*C)
 // gscale (device, 2 floats): upstream gradients of the two means (d loss / d Ll1, d loss / d ssim)
+// MASKED: the expression is evaluated on x = min(pred, cmax) * m and y = gt * m, as the forward formed them, and
+//         v_pred = m * [pred <= cmax] * (...): an exact 0.0 where m = 0 (there x = y = 0 and torch's sign(0) is 0 too)
+template <bool MASKED>
 __global__ __launch_bounds__(256) void l1_ssim_bwd_kernel(int H, int W, Win win, float cmax,
                                                           const float *__restrict__ pred,
                                                           const float *__restrict__ gt,
                                                           const float *__restrict__ dmaps,
                                                           const float *__restrict__ gscale,
-                                                          float *__restrict__ v_pred) {
+                                                          float *__restrict__ v_pred,
+                                                          const unsigned char *__restrict__ mask) {
     __shared__ float pm[3][PS][PS + 1];
     __shared__ float hm[3][PS][TS + 1];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
@@ -174,6 +216,9 @@ __global__ __launch_bounds__(256) void l1_ssim_bwd_kernel(int H, int W, Win win,
     const size_t plane = (size_t)Ho * Wo;
     const size_t pix = ((size_t)qy * W + qx) * 3;
     float out[3] = {0.f, 0.f, 0.f};
+    bool keep = true;
+    if constexpr (MASKED) keep = in_img && mask[(size_t)qy * W + qx] != 0;
+    [[maybe_unused]] const float mk = keep ? 1.f : 0.f;       // `* 1.0f` is exact: an all-ones mask changes no bit
     for (int c = 0; c < 3; ++c) {
         __syncthreads();
         // outputs p that see pixel q: p in [q - 10, q]; patch row r <-> p_y = y0 - 10 + r
@@ -223,12 +268,14 @@ __global__ __launch_bounds__(256) void l1_ssim_bwd_kernel(int H, int W, Win win,
                 b = fmaf(g, hm[1][ty + k][tx], b);
                 d = fmaf(g, hm[2][ty + k][tx], d);
             }
-            const float raw = pred[pix + c], y = gt[pix + c];
-            const float x = fminf(raw, cmax);
+            const float raw = pred[pix + c], yr = gt[pix + c];
+            const float xr = fminf(raw, cmax);
+            const float x = MASKED ? xr * mk : xr, y = MASKED ? yr * mk : yr;
             const float df = x - y;
             const float sgn = df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f);
             const float gval = fmaf(w_l1, sgn, w_ss * (a + 2.f * x * b + y * d));
             out[c] = (raw <= cmax) ? gval : 0.f;          // clamp passes the gradient where raw <= max
+            if constexpr (MASKED) out[c] = keep ? out[c] : 0.f;
         }
     }
     if (in_img) {
@@ -251,8 +298,8 @@ Win make_window(float sigma) {
 
 }  // namespace
 
-static size_t partial_bytes(int h, int w) {
-    return (((size_t)sgn_cdiv(w, TS) * sgn_cdiv(h, TS) * 2 * sizeof(float)) + 255) & ~(size_t)255;
+static size_t partial_bytes(int h, int w, int per_block = 2) {
+    return (((size_t)sgn_cdiv(w, TS) * sgn_cdiv(h, TS) * per_block * sizeof(float)) + 255) & ~(size_t)255;
 }
 
 // workspace = [per-workgroup partial sums][3 maps x 3 channels x (h-10) x (w-10) floats]
@@ -274,9 +321,9 @@ SGN_EXPORT int sgn_l1_ssim_fwd(int h, int w, const float *pred, const float *gt,
     const float C1 = (0.01f * data_range) * (0.01f * data_range), C2 = (0.03f * data_range) * (0.03f * data_range);
     const dim3 grid(sgn_cdiv(w, TS), sgn_cdiv(h, TS));
     sgn_timing_begin(SGN_T_LOSS_FWD, (void *)s);
-    hipLaunchKernelGGL(l1_ssim_fwd_kernel, grid, dim3(256), 0, s, h, w, win, C1, C2, clamp_max, pred, gt, partials,
-                       dmaps);
-    hipLaunchKernelGGL(l1_ssim_reduce_kernel, dim3(1), dim3(256), 0, s, (int)(grid.x * grid.y), partials,
+    hipLaunchKernelGGL((l1_ssim_fwd_kernel<false, false>), grid, dim3(256), 0, s, h, w, win, C1, C2, clamp_max, pred, gt,
+                       partials, dmaps, (const unsigned char *)nullptr);
+    hipLaunchKernelGGL(l1_ssim_reduce_kernel<false>, dim3(1), dim3(256), 0, s, (int)(grid.x * grid.y), partials,
                        1.f / (3.f * (float)h * (float)w), 1.f / (3.f * (float)(h - HALO) * (float)(w - HALO)),
                        ssim_lambda, out3);
     sgn_timing_end(SGN_T_LOSS_FWD, (void *)s);
@@ -293,8 +340,64 @@ SGN_EXPORT int sgn_l1_ssim_bwd(int h, int w, const float *pred, const float *gt,
     const float *dmaps = (const float *)((const char *)ws + partial_bytes(h, w));
     const Win win = make_window(1.5f);
     sgn_timing_begin(SGN_T_LOSS_BWD, (void *)s);
-    hipLaunchKernelGGL(l1_ssim_bwd_kernel, dim3(sgn_cdiv(w, TS), sgn_cdiv(h, TS)), dim3(256), 0, s, h, w, win,
-                       clamp_max, pred, gt, dmaps, gscale2, v_pred);
+    hipLaunchKernelGGL(l1_ssim_bwd_kernel<false>, dim3(sgn_cdiv(w, TS), sgn_cdiv(h, TS)), dim3(256), 0, s, h, w, win,
+                       clamp_max, pred, gt, dmaps, gscale2, v_pred, (const unsigned char *)nullptr);
+    sgn_timing_end(SGN_T_LOSS_BWD, (void *)s);
+    SGN_LAUNCH_CHECK();
+    return 0;
+}
+
+// The masked entry points (mask == NULL: no mask, still with the MSE slot).  Their workspace differs from the unmasked
+// one only in the partials' stride: [3 floats per workgroup][the same 9 maps].
+SGN_EXPORT size_t sgn_l1_ssim_masked_workspace_bytes(int h, int w, int with_grad) {
+    if (h <= HALO || w <= HALO) return 256;
+    return partial_bytes(h, w, 3) + (with_grad ? (size_t)9 * (h - HALO) * (w - HALO) * sizeof(float) : 0);
+}
+
+SGN_EXPORT int sgn_l1_ssim_masked_fwd(int h, int w, const float *pred, const float *gt, const unsigned char *mask,
+                                      float data_range, float clamp_max, float ssim_lambda,
+                                      float *out4 /*device: [Ll1, ssim, (1-l) Ll1 + l (1-ssim), mse]*/, int with_grad,
+                                      void *ws, size_t ws_bytes, sgn_stream_t stream) {
+    SGN_ARG_CHECK(h > HALO && w > HALO, -1);
+    SGN_ARG_CHECK(pred && gt && out4 && ws, -2);
+    SGN_ARG_CHECK(ws_bytes >= sgn_l1_ssim_masked_workspace_bytes(h, w, with_grad), -3);
+    hipStream_t s = (hipStream_t)stream;
+    float *partials = (float *)ws;
+    float *dmaps = with_grad ? (float *)((char *)ws + partial_bytes(h, w, 3)) : nullptr;
+    const Win win = make_window(1.5f);
+    const float C1 = (0.01f * data_range) * (0.01f * data_range), C2 = (0.03f * data_range) * (0.03f * data_range);
+    const dim3 grid(sgn_cdiv(w, TS), sgn_cdiv(h, TS));
+    sgn_timing_begin(SGN_T_LOSS_FWD, (void *)s);
+    if (mask)
+        hipLaunchKernelGGL((l1_ssim_fwd_kernel<true, true>), grid, dim3(256), 0, s, h, w, win, C1, C2, clamp_max, pred,
+                           gt, partials, dmaps, mask);
+    else
+        hipLaunchKernelGGL((l1_ssim_fwd_kernel<false, true>), grid, dim3(256), 0, s, h, w, win, C1, C2, clamp_max, pred,
+                           gt, partials, dmaps, mask);
+    hipLaunchKernelGGL(l1_ssim_reduce_kernel<true>, dim3(1), dim3(256), 0, s, (int)(grid.x * grid.y), partials,
+                       1.f / (3.f * (float)h * (float)w), 1.f / (3.f * (float)(h - HALO) * (float)(w - HALO)),
+                       ssim_lambda, out4);
+    sgn_timing_end(SGN_T_LOSS_FWD, (void *)s);
+    SGN_LAUNCH_CHECK();
+    return 0;
+}
+
+SGN_EXPORT int sgn_l1_ssim_masked_bwd(int h, int w, const float *pred, const float *gt, const unsigned char *mask,
+                                      float clamp_max, const void *ws, const float *gscale2, float *v_pred,
+                                      sgn_stream_t stream) {
+    SGN_ARG_CHECK(h > HALO && w > HALO, -1);
+    SGN_ARG_CHECK(pred && gt && ws && gscale2 && v_pred, -2);
+    hipStream_t s = (hipStream_t)stream;
+    const float *dmaps = (const float *)((const char *)ws + partial_bytes(h, w, 3));
+    const Win win = make_window(1.5f);
+    const dim3 grid(sgn_cdiv(w, TS), sgn_cdiv(h, TS));
+    sgn_timing_begin(SGN_T_LOSS_BWD, (void *)s);
+    if (mask)
+        hipLaunchKernelGGL(l1_ssim_bwd_kernel<true>, grid, dim3(256), 0, s, h, w, win, clamp_max, pred, gt, dmaps, gscale2,
+                           v_pred, mask);
+    else
+        hipLaunchKernelGGL(l1_ssim_bwd_kernel<false>, grid, dim3(256), 0, s, h, w, win, clamp_max, pred, gt, dmaps, gscale2,
+                           v_pred, mask);
     sgn_timing_end(SGN_T_LOSS_BWD, (void *)s);
     SGN_LAUNCH_CHECK();
     return 0;

@@ -11,6 +11,9 @@ with ``self.ssim = pytorch_msssim.SSIM(data_range=1.0, size_average=True, channe
 ABI (``sgn_l1_ssim_fwd/bwd``) directly on the rasterizer's HWC image; fails loudly without the HIP library.
 
 * :func:`l1_ssim` — ``(Ll1, ssim)`` of two [H,W,3] images, gradient to ``pred``.
+* ``mask=`` on :func:`l1_ssim` / :func:`photometric_loss` — the batch's boolean pixel mask (``:1081-1083``:
+  ``gt_img *= mask; rgb *= mask``) folded into the same two kernels (``sgn_l1_ssim_masked_fwd/bwd``).
+* :func:`image_metrics` — ``(psnr, ssim)`` of the evaluation path (``:1135-1151``), one no-grad forward.
 * :class:`SSIM` — ``pytorch_msssim.SSIM`` call shape (``forward(X, Y)`` on [1,3,H,W]) for the import shim; the
   permuted views the reference passes are recognised and used in place (no NCHW copy).
 * :func:`sky_accumulation`, :func:`object_acc_entropy`, :func:`accumulation_losses` — the two accumulation
@@ -26,13 +29,39 @@ import torch
 from . import _lib as L
 
 
-def _forward(ctx, pred, gt, data_range, clamp_max, ssim_lambda):
-    L.require_device(pred, gt)
+def check_mask(mask, h: int, w: int) -> None:
+    """Host-side validation of a pixel mask for an ``h`` x ``w`` image, before anything is launched: a ``bool`` or
+    ``uint8`` tensor of shape [H,W] or [H,W,1] (the reference's batch["mask"]).  Any other dtype is a ``TypeError``: a
+    float image would be a weight map, which the reference does not have."""
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
+        what = mask.dtype if isinstance(mask, torch.Tensor) else type(mask).__name__
+        raise TypeError(f"mask must be a bool or uint8 tensor (non-zero = keep), got {what}")
+    if tuple(mask.shape) not in ((h, w), (h, w, 1)):
+        raise ValueError(f"mask must have the image's {h * w} pixels as [{h},{w}] or [{h},{w},1], "
+                         f"got {tuple(mask.shape)}")
+
+
+def _mask_bytes(mask: torch.Tensor) -> torch.Tensor:
+    """The mask as contiguous uint8 [H*W...]; a contiguous ``bool`` is viewed, not copied.  No gradient."""
+    m = mask.detach().contiguous()
+    return m.view(torch.uint8) if m.dtype == torch.bool else m
+
+
+def _check_images(pred, gt):
     if pred.dim() != 3 or pred.shape[-1] != 3 or pred.shape != gt.shape:
         raise ValueError(f"l1_ssim expects two [H,W,3] images, got {tuple(pred.shape)} and {tuple(gt.shape)}")
     h, w = pred.shape[0], pred.shape[1]
     if min(h, w) <= 10:
         raise ValueError("images must be larger than the 11-tap SSIM window")   # pytorch_msssim asserts too
+    return h, w
+
+
+def _forward(ctx, pred, gt, data_range, clamp_max, ssim_lambda, mask=None):
+    if mask is not None:
+        return _forward_masked(ctx, pred, gt, data_range, clamp_max, ssim_lambda, mask,
+                               bool(ctx.needs_input_grad[0]))
+    L.require_device(pred, gt)
+    h, w = _check_images(pred, gt)
     p, g = pred.contiguous().float(), gt.contiguous().float()
     lib = L.load()
     out3 = torch.empty(3, dtype=torch.float32, device=p.device)
@@ -41,14 +70,42 @@ def _forward(ctx, pred, gt, data_range, clamp_max, ssim_lambda):
     cmax = float("inf") if clamp_max is None else float(clamp_max)
     L.check(lib.sgn_l1_ssim_fwd(h, w, L.ptr(p), L.ptr(g), float(data_range), cmax, float(ssim_lambda), L.ptr(out3),
                                 need_grad, L.ptr(maps), maps.numel(), L.stream_ptr()), "sgn_l1_ssim_fwd")
-    ctx.hw, ctx.cmax, ctx.maps = (h, w), cmax, maps
+    ctx.hw, ctx.cmax, ctx.maps, ctx.masked = (h, w), cmax, maps, False
     ctx.save_for_backward(p, g)
     return out3
 
 
+def _forward_masked(ctx, pred, gt, data_range, clamp_max, ssim_lambda, mask, need_grad):
+    """The masked entry points: ``out4 = [Ll1, ssim, weighted sum, mse]`` of ``min(pred, clamp_max) * m`` and
+    ``gt * m``; ``mask`` may be ``None`` here (the metrics without a mask).  ``ctx`` None: nothing kept for a backward."""
+    if pred.dim() == 3 and mask is not None:
+        check_mask(mask, pred.shape[0], pred.shape[1])                 # TypeError / ValueError before the device check
+    L.require_device(pred, gt, mask)
+    h, w = _check_images(pred, gt)
+    p, g = pred.contiguous().float(), gt.contiguous().float()
+    m = None if mask is None else _mask_bytes(mask)
+    lib = L.load()
+    out4 = torch.empty(4, dtype=torch.float32, device=p.device)
+    maps = L.workspace(lib.sgn_l1_ssim_masked_workspace_bytes(h, w, int(need_grad)), p.device)
+    cmax = float("inf") if clamp_max is None else float(clamp_max)
+    L.check(lib.sgn_l1_ssim_masked_fwd(h, w, L.ptr(p), L.ptr(g), L.ptr(m), float(data_range), cmax, float(ssim_lambda),
+                                       L.ptr(out4), int(need_grad), L.ptr(maps), maps.numel(), L.stream_ptr()),
+            "sgn_l1_ssim_masked_fwd")
+    if ctx is not None:
+        ctx.hw, ctx.cmax, ctx.maps, ctx.masked = (h, w), cmax, maps, True
+        ctx.save_for_backward(p, g, m)
+    return out4
+
+
 def _backward(ctx, gscale):
-    p, g = ctx.saved_tensors
     h, w = ctx.hw
+    if ctx.masked:
+        p, g, m = ctx.saved_tensors
+        v = torch.empty_like(p)
+        L.check(L.load().sgn_l1_ssim_masked_bwd(h, w, L.ptr(p), L.ptr(g), L.ptr(m), ctx.cmax, L.ptr(ctx.maps),
+                                                L.ptr(gscale), L.ptr(v), L.stream_ptr()), "sgn_l1_ssim_masked_bwd")
+        return v
+    p, g = ctx.saved_tensors
     v = torch.empty_like(p)
     L.check(L.load().sgn_l1_ssim_bwd(h, w, L.ptr(p), L.ptr(g), ctx.cmax, L.ptr(ctx.maps), L.ptr(gscale), L.ptr(v),
                                      L.stream_ptr()), "sgn_l1_ssim_bwd")
@@ -57,14 +114,14 @@ def _backward(ctx, gscale):
 
 class _L1SSIM(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pred, gt, data_range, clamp_max):
-        out3 = _forward(ctx, pred, gt, data_range, clamp_max, 0.0)
+    def forward(ctx, pred, gt, data_range, clamp_max, mask=None):
+        out3 = _forward(ctx, pred, gt, data_range, clamp_max, 0.0, mask)
         return out3[0], out3[1]
 
     @staticmethod
     def backward(ctx, g_l1, g_ssim):
         gscale = torch.stack([g_l1.reshape(()), g_ssim.reshape(())]).float().contiguous()
-        return _backward(ctx, gscale), None, None, None
+        return _backward(ctx, gscale), None, None, None, None
 
 
 _LAMBDA_VEC: dict = {}
@@ -75,8 +132,8 @@ class _Photometric(torch.autograd.Function):
     turns the upstream scalar into the two weights with a single tiny multiply."""
 
     @staticmethod
-    def forward(ctx, pred, gt, ssim_lambda, clamp_max):
-        out3 = _forward(ctx, pred, gt, 1.0, clamp_max, ssim_lambda)
+    def forward(ctx, pred, gt, ssim_lambda, clamp_max, mask=None):
+        out3 = _forward(ctx, pred, gt, 1.0, clamp_max, ssim_lambda, mask)
         ctx.lam = float(ssim_lambda)
         return out3[2]
 
@@ -86,20 +143,48 @@ class _Photometric(torch.autograd.Function):
         if key not in _LAMBDA_VEC:
             _LAMBDA_VEC[key] = torch.tensor([1.0 - ctx.lam, -ctx.lam], dtype=torch.float32, device=g.device)
         gscale = (_LAMBDA_VEC[key] * g.reshape(())).contiguous()
-        return _backward(ctx, gscale), None, None, None
+        return _backward(ctx, gscale), None, None, None, None
 
 
-def l1_ssim(pred: torch.Tensor, gt: torch.Tensor, data_range: float = 1.0, clamp_max=None):
+def l1_ssim(pred: torch.Tensor, gt: torch.Tensor, data_range: float = 1.0, clamp_max=None, mask=None):
     """(mean |gt - pred|, SSIM(gt, pred)) for [H,W,3] images; differentiable w.r.t. ``pred``.
     ``clamp_max`` folds the caller's ``torch.clamp(rgb, max=clamp_max)`` (``sgn_splatfacto.py:969``) into the kernels:
-    ``pred`` is read as ``min(pred, clamp_max)`` and the gradient is zero where ``pred > clamp_max``."""
-    return _L1SSIM.apply(pred, gt, data_range, clamp_max)
+    ``pred`` is read as ``min(pred, clamp_max)`` and the gradient is zero where ``pred > clamp_max``.
+
+    ``mask`` ([H,W] or [H,W,1], ``bool`` or ``uint8``, non-zero = keep) is the reference's batch["mask"]
+    (``:1081-1083``): both terms are taken of ``min(pred, clamp_max) * mask`` and ``gt * mask``.  As in the reference the
+    means keep their unmasked denominators (3HW and 3(H-10)(W-10): nothing is normalised by the number of kept
+    pixels), SSIM windows that straddle the mask edge see zeros on both images, and the clamp comes before the mask.
+    The gradient is an exact 0 at masked pixels; the mask gets none; unlike the reference, neither ``pred`` nor ``gt``
+    is modified.  ``mask=None`` is the unmasked path, unchanged."""
+    if mask is None:
+        return _L1SSIM.apply(pred, gt, data_range, clamp_max)
+    return _L1SSIM.apply(pred, gt, data_range, clamp_max, mask)
 
 
-def photometric_loss(pred: torch.Tensor, gt: torch.Tensor, ssim_lambda: float = 0.2, clamp_max=None) -> torch.Tensor:
+def photometric_loss(pred: torch.Tensor, gt: torch.Tensor, ssim_lambda: float = 0.2, clamp_max=None,
+                     mask=None) -> torch.Tensor:
     """``(1 - l) * Ll1 + l * (1 - ssim)`` — the sum of losses["Ll1"] and losses["simloss"] (``:1086-1087``), one
-    forward and one backward kernel plus a single scalar multiply."""
-    return _Photometric.apply(pred, gt, ssim_lambda, clamp_max)
+    forward and one backward kernel plus a single scalar multiply.  ``mask``: see :func:`l1_ssim`."""
+    if mask is None:
+        return _Photometric.apply(pred, gt, ssim_lambda, clamp_max)
+    return _Photometric.apply(pred, gt, ssim_lambda, clamp_max, mask)
+
+
+def _metrics_out4(pred: torch.Tensor, gt: torch.Tensor, mask=None, data_range: float = 1.0) -> torch.Tensor:
+    """``[Ll1, ssim, Ll1, mse]`` of the (masked) images: one forward launch plus the reduce, no graph, no clamp."""
+    with torch.no_grad():
+        return _forward_masked(None, pred.detach(), gt.detach(), data_range, None, 0.0, mask, False)
+
+
+def image_metrics(pred: torch.Tensor, gt: torch.Tensor, mask=None, data_range: float = 1.0):
+    """``(psnr, ssim)`` of two [H,W,3] images as the reference's evaluation computes them (``:1135-1151``: ``gt *
+    mask``, ``rgb * mask``, then ``PeakSignalNoiseRatio(data_range=1.0)`` and ``SSIM``): ``psnr = 10 log10(data_range^2 /
+    mse)`` with ``mse`` the mean over all 3HW elements of the masked images (identical images: ``+inf``).  0-dim device
+    tensors without an autograd graph and without a host sync.  ``mask`` as in :func:`l1_ssim`."""
+    out4 = _metrics_out4(pred, gt, mask, data_range)
+    psnr = 10.0 * torch.log10(float(data_range) ** 2 / out4[3].double())
+    return psnr.float(), out4[1]
 
 
 def _as_hwc(t: torch.Tensor) -> torch.Tensor:

@@ -316,14 +316,22 @@ def train_step(P: Dict[str, torch.Tensor], cam: Camera, w_img: torch.Tensor, w_a
                sh_degree_to_use: int = 3, block_width: int = 16, with_depth: bool = False, ops=_hip_ops,
                reducer=None, fused: bool = False, sky: Optional[dict] = None, gt: Optional[torch.Tensor] = None,
                ssim_lambda: float = 0.2, loss_fn=None, caller_syncs: bool = False, zero_grad: bool = True,
-               **fused_kw) -> SimpleNamespace:
+               mask: Optional[torch.Tensor] = None, **fused_kw) -> SimpleNamespace:
     """One "train-step image": project fwd -> SH fwd -> rasterize(return_alpha) fwd -> scalar loss ->
     full backward to means / log-scales / raw quats / opacity logits / SH coefficients (the metric's definition,
     SURVEY.md §8d: the operator sequence; ``caller_syncs=True`` adds the two host syncs of the reference's own model
     code, sgn_splatfacto.py:878,944, as the scene-graph replay always does).  ``sky`` =
     {"base": cube map leaf [6,R,R,3], "c2w": [3,4]} adds the reference's sky-sphere branch.  ``gt`` [H,W,3] swaps the
     synthetic linear image loss for the reference's photometric loss (``sgn_splatfacto.py:1084-1087``: (1-l) L1 + l
-    (1 - SSIM) on ``rgb.clamp(max=1)``), through ``sgn_rast.loss`` or the ``loss_fn(rgb, gt, l)`` the tests pass."""
+    (1 - SSIM) on ``rgb.clamp(max=1)``), through ``sgn_rast.loss`` or the ``loss_fn(rgb, gt, l)`` the tests pass.
+    ``mask`` (bool / uint8 [H,W] or [H,W,1]) is the batch's pixel mask of that loss (``:1081-1083``), see
+    ``sgn_rast.loss.l1_ssim``; a ``loss_fn`` receives it as the keyword ``mask`` only when it is given."""
+    if mask is not None:           # host-side errors first: before the render, let alone the loss, launches anything
+        if gt is None:
+            raise ValueError("mask applies to the photometric loss: pass gt as well")
+        if loss_fn is None:
+            from .loss import check_mask
+            check_mask(mask, cam.height, cam.width)
     if zero_grad:                  # (False: the caller's loop owns the gradients — keeps and accumulates them, or resets them)
         for p in P.values():
             p.grad = None
@@ -341,10 +349,10 @@ def train_step(P: Dict[str, torch.Tensor], cam: Camera, w_img: torch.Tensor, w_a
     if gt is not None:
         if loss_fn is not None:                                                        # tests: the oracle's loss
             rgb = out.rgb if sky is not None else torch.clamp(out.rgb, max=1.0)        # :969 (sky path clamps inside)
-            photo = loss_fn(rgb, gt, ssim_lambda)
+            photo = loss_fn(rgb, gt, ssim_lambda) if mask is None else loss_fn(rgb, gt, ssim_lambda, mask=mask)
         else:
             from .loss import photometric_loss
-            photo = photometric_loss(out.rgb, gt, ssim_lambda, clamp_max=None if sky is not None else 1.0)
+            photo = photometric_loss(out.rgb, gt, ssim_lambda, clamp_max=None if sky is not None else 1.0, mask=mask)
         loss = photo + (out.alpha * w_a).sum() / n_pix
     else:
         loss = ((out.rgb * w_img).sum() + (out.alpha * w_a).sum()) / n_pix

@@ -301,19 +301,28 @@ def render_views(P: Dict[str, torch.Tensor], cams: Sequence[Camera], sh_degree_t
 
 
 def train_step_views(P: Dict[str, torch.Tensor], cams: Sequence[Camera], gts: Sequence[torch.Tensor],
-                     ssim_lambda: float = 0.2, sh_degree_to_use: int = 3, zero_grad: bool = True) -> SimpleNamespace:
+                     ssim_lambda: float = 0.2, sh_degree_to_use: int = 3, zero_grad: bool = True,
+                     masks: Optional[Sequence[Optional[torch.Tensor]]] = None) -> SimpleNamespace:
     """One multi-view step: :func:`render_views`, then the mean over the views of the per-view photometric loss of
     :mod:`sgn_rast.loss` ((1-l) L1 + l (1 - SSIM) on ``rgb.clamp(max=1)``, each view on its own: no SSIM window spans two
-    views) — the data-parallel path's averaged-gradient semantics (``sgn_rast/dp.py``) on one GPU — and the backward."""
-    from .loss import photometric_loss
+    views) — the data-parallel path's averaged-gradient semantics (``sgn_rast/dp.py``) on one GPU — and the backward.
+    ``masks``: one pixel mask per view (``sgn_rast.loss.l1_ssim``'s ``mask``; an entry may be ``None``)."""
+    from .loss import check_mask, photometric_loss
     if len(gts) != len(cams):
         raise ValueError(f"{len(cams)} cameras but {len(gts)} ground-truth images")
+    if masks is None:
+        masks = [None] * len(cams)
+    if len(masks) != len(cams):
+        raise ValueError(f"{len(cams)} cameras but {len(masks)} masks")
+    for c, m in zip(cams, masks):
+        if m is not None:
+            check_mask(m, c.height, c.width)
     if zero_grad:
         for p in P.values():
             p.grad = None
     out = render_views(P, cams, sh_degree_to_use)
     b = len(cams)
-    loss = sum(photometric_loss(out.rgb[v], gts[v], ssim_lambda, clamp_max=1.0) for v in range(b)) / b
+    loss = sum(photometric_loss(out.rgb[v], gts[v], ssim_lambda, clamp_max=1.0, mask=masks[v]) for v in range(b)) / b
     loss.backward()
     out.loss = loss.detach()
     return out
