@@ -759,6 +759,23 @@ int sgn_knn(int n, int k, const float *points /*[n,3]*/, float *dist /*[n,k]*/, 
             int64_t *visited /*nullable: device int64, += candidate distances evaluated*/, void *ws, size_t ws_bytes,
             sgn_stream_t stream);
 
+/* NEAREST NEIGHBOUR ACROSS TWO CLOUDS (the primitive of the reference's LiDAR chamfer metric,
+ * street_gaussians_ns/data/utils/geometric_metric.py:59-69: open3d's compute_point_cloud_distance, the exact distance to
+ * the nearest point of the other cloud).  For every row q of query [n_query,3]: dist[q] = the smallest |query_q - target_j|
+ * over ALL rows j of target [n_target,3] as an fp32 direct difference, idx[q] = that j (idx nullable; no row is excluded:
+ * the clouds are unrelated; on equal distances the choice among them is this library's).  Finite fp32 input; non-finite
+ * input gives unspecified rows, never an out-of-bounds access.  1 <= n_target, n_query <= 2^30 (else rc < 0).  The tree of
+ * sgn_knn is built over the target, the queries are sorted along the target's Morton curve and 64 neighbouring queries
+ * walk the tree together (n_query * 16 <= n_target: one wave per query instead, no query sort).  Deterministic:
+ * bit-identical results for the same input.  visited (nullable, device int64): ADDS the number of candidate distances
+ * evaluated.  Asynchronous on `stream`, no host synchronisation;
+ * ws >= sgn_cloud_nn_workspace_bytes(n_target, n_query), which depends on the two counts only (0 when one is out of
+ * range).  csrc/cloud_nn.hip. */
+size_t sgn_cloud_nn_workspace_bytes(int n_target, int n_query);
+int sgn_cloud_nn(int n_target, const float *target /*[n_target,3]*/, int n_query, const float *query /*[n_query,3]*/,
+                 float *dist /*[n_query]*/, int32_t *idx /*[n_query], may be NULL*/, int64_t *visited /*may be NULL*/,
+                 void *ws, size_t ws_bytes, sgn_stream_t stream);
+
 /* BATCHED VIEWS (no upstream counterpart; gsplat 1.x takes [C] cameras per call).  B = n_views cameras share one image
  * size (img_h, img_w), 16x16 tiles and one set of N Gaussians in the fused front end's raw form (means, log-scales, raw
  * quaternions, opacity logits, features_dc [N,1,3], features_rest [N,k-1,3]; no scene graph).  Row b*N + i of every

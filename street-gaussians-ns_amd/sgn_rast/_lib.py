@@ -130,6 +130,8 @@ SIGNATURES = {
                                          _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _i, _vp, _vp, _vp]),
     "sgn_knn_workspace_bytes": (_sz, [_i, _i]),
     "sgn_knn": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sgn_cloud_nn_workspace_bytes": (_sz, [_i, _i]),
+    "sgn_cloud_nn": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None
