@@ -1,7 +1,9 @@
 """Masked L1 + SSIM loss and the image metrics (csrc/loss.hip masked instantiations via sgn_l1_ssim_masked_fwd/bwd)
 against the unchanged oracle applied to the reference's literal expressions (sgn_splatfacto.py:1081-1087, 1135-1151):
 ``O.l1_ssim_losses(torch.clamp(p, max=1) * m, gt * m)`` with autograd, and ``10 log10(1 / mean((gt m - p m)^2))`` in
-fp64.  Tolerances are the ones tests/test_gpu_loss.py uses for the same kernels and reductions."""
+fp64.  Tolerances are the ones tests/test_gpu_loss.py uses for the same kernels and reductions.  The content here is white
+noise with sigma^2 >> C2 in every window; the smooth, near-converged regime is held per pixel against fp64 in
+tests/test_gpu_loss_per_pixel.py."""
 import math
 
 import pytest
