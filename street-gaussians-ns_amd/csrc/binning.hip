@@ -893,15 +893,6 @@ static Cull make_cull(const float *conics, const float *opac, int opac_is_logit,
     return c;
 }
 
-// `total_host`: device-visible pointer into pinned host memory (or nullptr) that receives cum_by_rank[n-1] from the scan
-// itself (api.cpp sgn_rasterize_fwd_all: the count's read-back without a copy command)
-int sgn_bin_prepare_total(int n, const float *xys, const float *depths, const int32_t *radii,
-                          const float *conics, const float *opacities, int opacity_is_logit, int cull,
-                          int tiles_x, int tiles_y, int block_width, int32_t *cum_by_rank,
-                          int32_t *gid_by_rank, int rank_ready, float *bin_records, void *ws, size_t ws_bytes,
-                          int sort_rank_mode, int32_t *total_host, const int32_t *extra_dev, int32_t *extra_host,
-                          int semantics, sgn_stream_t stream);
-
 SGN_EXPORT int sgn_bin_prepare(int n, const float *xys, const float *depths, const int32_t *radii,
                                const float *conics, const float *opacities, int opacity_is_logit, int cull,
                                int tiles_x, int tiles_y, int block_width, int32_t *cum_by_rank,
@@ -953,14 +944,6 @@ SGN_EXPORT size_t sgn_bin_intersect_workspace_bytes(int64_t n_isect) {
     const size_t ni = (size_t)(n_isect > 0 ? n_isect : 1);
     return 3 * al256(ni * 4) + sgn_sort_pairs32_ws_bytes(n_isect);
 }
-
-// `also_zero_words`: int32 words BEHIND tile_bins' 2 * n_tiles that the emission clears as well (the composite forward
-// puts the raster kernels' tile statistics there: one more clear that needs no launch of its own)
-int sgn_bin_intersect_zero(int n, int64_t n_isect, const float *bin_records, const int32_t *cum_by_rank,
-                           const int32_t *gid_by_rank, int tiles_x, int tiles_y, int block_width,
-                           int32_t *gaussian_ids_sorted, int32_t *tile_bins, int quadrant_masks, void *ws,
-                           size_t ws_bytes, const int32_t *n_isect_dev, int sort_rank_mode, int also_zero_words,
-                           sgn_stream_t stream);
 
 SGN_EXPORT int sgn_bin_intersect(int n, int64_t n_isect, const float *bin_records, const int32_t *cum_by_rank,
                                  const int32_t *gid_by_rank, int tiles_x, int tiles_y, int block_width,

@@ -40,6 +40,7 @@ int sgn_fork_events(hipEvent_t *fork, hipEvent_t *join);   // api.cpp: cached pe
         }                                                                      \
     } while (0)
 
+// ---- internal entry points that api.cpp's one-call entries are built from (not part of include/sgn_rast.h)
 // project.hip: sgn_project_fwd with upstream's unit-quaternion assertion riding the kernel (quat_flag nullptr: none); a
 // failing row stores quat_stamp into *quat_flag, and — quat_ok != nullptr — the kernel's first lane stores it into
 // *quat_ok ("this launch's stores land where the host looks"); both system-scope
@@ -48,6 +49,49 @@ int sgn_project_fwd_checked(int n, const float *means3d, const float *scales, fl
                             int block_width, float clip_thresh, float *cov3d, float *xys, float *depths, int32_t *radii,
                             float *conics, float *compensation, int32_t *num_tiles_hit, int32_t *quat_flag,
                             float quat_tol, int32_t quat_stamp, int32_t *quat_ok, int semantics, sgn_stream_t stream);
+// project.hip: one wave copies n words (<= 64) into mapped pinned memory, then stores flag_value into *flag_mapped
+int sgn_publish_words(const int32_t *src_dev, int n, int32_t *dst_mapped, int32_t *flag_mapped, int32_t flag_value,
+                      sgn_stream_t stream);
+// binning.hip: sgn_bin_prepare; `total_host`: device-visible pointer into pinned host memory (or nullptr) that receives
+// cum_by_rank[n-1] from the scan itself, `extra_dev` -> `extra_host` one more word stored ahead of it
+int sgn_bin_prepare_total(int n, const float *xys, const float *depths, const int32_t *radii,
+                          const float *conics, const float *opacities, int opacity_is_logit, int cull,
+                          int tiles_x, int tiles_y, int block_width, int32_t *cum_by_rank,
+                          int32_t *gid_by_rank, int rank_ready, float *bin_records, void *ws, size_t ws_bytes,
+                          int sort_rank_mode, int32_t *total_host, const int32_t *extra_dev, int32_t *extra_host,
+                          int semantics, sgn_stream_t stream);
+// binning.hip: sgn_bin_intersect; `also_zero_words`: int32 words BEHIND tile_bins' 2 * n_tiles that the emission clears
+// as well (the one-call forward puts the raster kernels' tile statistics there: a clear that needs no launch of its own)
+int sgn_bin_intersect_zero(int n, int64_t n_isect, const float *bin_records, const int32_t *cum_by_rank,
+                           const int32_t *gid_by_rank, int tiles_x, int tiles_y, int block_width,
+                           int32_t *gaussian_ids_sorted, int32_t *tile_bins, int quadrant_masks, void *ws,
+                           size_t ws_bytes, const int32_t *n_isect_dev, int sort_rank_mode, int also_zero_words,
+                           sgn_stream_t stream);
+// binning.hip: the same over n = n_views * n_per_view rows of one depth ranking, 16x16 tiles
+int sgn_bin_intersect_views(int n_views, int n, int64_t n_isect, const float *bin_records, const int32_t *cum_by_rank,
+                            const int32_t *gid_by_rank, int tiles_x, int tiles_y, int32_t *gaussian_ids_sorted,
+                            int32_t *tile_bins, int quadrant_masks, void *ws, size_t ws_bytes,
+                            const int32_t *n_isect_dev, int sort_rank_mode, int also_zero_words, sgn_stream_t stream);
+// raster.hip: sgn_raster_fwd (full scene, rows built) behind a launch that already cleared tile_kmax
+int sgn_raster_fwd_precleared(int img_h, int img_w, int block_width, int n, int64_t n_isect,
+                              const int32_t *gaussian_ids_sorted, const int32_t *tile_bins, const float *xys,
+                              const float *conics, const float *colors, const float *opacities,
+                              int opacity_is_logit, const float *background3, float *out_img, float *final_Ts,
+                              int32_t *final_idx, void *recs_ws, size_t recs_ws_bytes, const int32_t *tile_order,
+                              int32_t *tile_kmax, const float *depths, float *out_depth, const sgn_raster_opts *opts,
+                              sgn_stream_t stream);
+// raster.hip: host side of the batched views' raster passes
+int sgn_views_repeat(int n, int n_views, const float *src, float *dst, sgn_stream_t stream);
+int sgn_raster_views_fwd(int n_views, int img_h, int img_w, const int32_t *ids, const int32_t *tile_bins,
+                         const void *rows, const float *background3, float *out_img, float *final_Ts,
+                         int32_t *final_idx, const int32_t *tile_order, int32_t *tile_kmax, const float *depths,
+                         float *out_depth, const sgn_raster_opts *opts, sgn_stream_t stream);
+int sgn_raster_views_bwd(int n_views, int n, int img_h, int img_w, const int32_t *ids, const int32_t *tile_bins,
+                         const void *rows, const float *conics, const float *logits, const float *background3,
+                         const float *final_Ts, const int32_t *final_idx, const float *v_out_img,
+                         const float *v_out_alpha, float alpha_clamp_bwd, float *v_xy, float *v_conic, float *v_colors,
+                         float *v_opacity, void *grad_ws, const int32_t *tile_order, const sgn_raster_opts *opts,
+                         sgn_stream_t stream, sgn_stream_t aux_stream);
 
 // Batched views (include/sgn_rast.h "Batched views"): the camera table travels BY VALUE as a kernel argument (SGPRs /
 // the kernarg segment, no device buffer, no copy), one entry per view; the host fills it from sgn_view_cam rows.

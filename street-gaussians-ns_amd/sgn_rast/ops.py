@@ -945,6 +945,14 @@ def bin_gaussians_fused(num_points, xys, depths, radii, num_tiles_hit, tile_boun
     return n_isect, _ids_only(ids), bins
 
 
+def _side_row(S):
+    """The next row (8 words) of the stream's pinned side-word pool; rotating: a read-back that is still pending keeps
+    its own row."""
+    if S.side is None:
+        S.side = [torch.empty(4, 8, dtype=torch.int32).pin_memory(), 0]
+    pool = S.side
+    pool[1] += 1
+    return pool[0][(pool[1] - 1) % 4]
 
 
 def _bin_prepare_async(num_points, xys, depths, radii, num_tiles_hit, tile_bounds, block_width, conics, opacity,
@@ -977,11 +985,7 @@ def _bin_prepare_async(num_points, xys, depths, radii, num_tiles_hit, tile_bound
                                 L.sort_rank_mode(), semantics().flags(), L.stream_ptr()),
             "sgn_bin_prepare")
     S = _S()
-    if S.side is None:
-        S.side = [torch.empty(4, 8, dtype=torch.int32).pin_memory(), 0]
-    pool = S.side
-    pinned = pool[0][pool[1] % 4]          # rotate: a prepare that is still pending keeps its own slot
-    pool[1] += 1
+    pinned = _side_row(S)
     # pending argument checks ride along: their flags reach the host in the same transfer as the count, so the
     # deferred assertion costs no round trip of its own.  The copies are queued on the current stream (a side stream
     # would add an event hop of ~15 us before the copy even starts); work queued afterwards simply follows them.
@@ -1102,22 +1106,13 @@ def _tile_order(tile_bins: torch.Tensor, tile_kmax: Optional[torch.Tensor] = Non
     n_tiles = tile_bins.shape[0]
     order = torch.empty(n_tiles + 2, dtype=torch.int32, device=tile_bins.device)   # permutation, n_long, cursor
     lib = L.load()
-    S = _S()
-    scratch = S.order_scratch.get(n_tiles) if tile_order_multiblock else None
-    if scratch is None and tile_order_multiblock:
-        # zero-filled once per (stream, tile count); every launch leaves it zero-filled (include/sgn_rast.h)
-        if len(S.order_scratch) > 8:
-            S.order_scratch.clear()
-        scratch = S.order_scratch[n_tiles] = torch.zeros(int(lib.sgn_tile_order_scratch_bytes(n_tiles)) // 4,
-                                                         dtype=torch.int32, device=tile_bins.device)
+    scratch = _order_scratch(_S(), lib, n_tiles, tile_bins.device)
     L.check(lib.sgn_tile_order(n_tiles, L.ptr(tile_bins), L.ptr(tile_kmax), int(long_thresh),
                                int(small_splat_q16) if (tile_kmax is not None and pairs_known) else 0, L.ptr(order),
                                L.ptr(scratch),
                                4 * scratch.numel() if scratch is not None else 0, L.stream_ptr()), "sgn_tile_order")
     if tile_kmax is None:
-        oc[ok] = (tile_bins, order)          # (keeps tile_bins alive: its id cannot be recycled while the entry lives)
-        while len(oc) > 4:
-            oc.popitem(last=False)
+        _remember_order(_S(), tile_bins, long_thresh, order)
     return order
 
 
@@ -1306,11 +1301,7 @@ def _match_window(key_tail, n, xys, depths, radii, num_tiles_hit, conics, opacit
             w[i] = f[i] = None
     L.check(lib.sgn_rows_match(n, n_full, len(cands), lo_host, *[L.ptr(t) for t in w], *[L.ptr(t) for t in f],
                                L.ptr(flags), L.stream_ptr()), "sgn_rows_match")
-    if S.side is None:
-        S.side = [torch.empty(4, 8, dtype=torch.int32).pin_memory(), 0]
-    pool = S.side
-    pinned = pool[0][pool[1] % 4]
-    pool[1] += 1
+    pinned = _side_row(S)
     pinned[0:len(cands)].copy_(flags[0:len(cands)], non_blocking=True)
     done = torch.cuda.Event()
     done.record()
@@ -1466,20 +1457,10 @@ def _forward_composite(S, key, _t, cull, n, xys_c, depths, radii, conics_c, colo
     order = torch.empty(n_tiles + 2, **i32)
     rows = L.workspace(lib.sgn_raster_workspace_bytes(n, 0, ro_ptr), dev)
     arena = L.workspace(lib.sgn_rasterize_arena_bytes(n, cap), dev)
-    scratch = None
-    if tile_order_enabled and tile_order_multiblock:
-        scratch = S.order_scratch.get(n_tiles)
-        if scratch is None:
-            if len(S.order_scratch) > 8:
-                S.order_scratch.clear()
-            scratch = S.order_scratch[n_tiles] = torch.zeros(int(lib.sgn_tile_order_scratch_bytes(n_tiles)) // 4, **i32)
+    scratch = _order_scratch(S, lib, n_tiles, dev)
     early_entry = S.early["entry"]
     early = _take_early_rank(depths, radii)
-    if S.side is None:
-        S.side = [torch.empty(4, 8, dtype=torch.int32).pin_memory(), 0]
-    pool = S.side
-    pinned = pool[0][pool[1] % 4]
-    pool[1] += 1
+    pinned = _side_row(S)
     walk_stat, S.walk_stat = S.walk_stat, None          # the last backward's walked / listed statistic rides along
     if walk_stat is not None and S.walked_permille is not None and S.stat_skipped < 7:
         S.stat_skipped += 1
@@ -1523,15 +1504,22 @@ def _forward_composite(S, key, _t, cull, n, xys_c, depths, radii, conics_c, colo
     if binning_cache_enabled:
         S.store_binning(key, tuple(t.detach() for t in _t), (count, ids, tile_bins), _window_info(_t, cull, logit_leaves))
     if tile_order_enabled:
-        oc = S.order_cache
-        oc[(id(tile_bins), _fwd_long_thresh(ro, block_width))] = (tile_bins, order)
-        while len(oc) > 4:
-            oc.popitem(last=False)
+        _remember_order(S, tile_bins, _fwd_long_thresh(ro, block_width), order)
     return count, ids, tile_bins, order, tile_kmax, rows
 
 
+def _remember_order(S, tile_bins, long_thresh, order):
+    """Keep a forward launch order for every later pass over the same bins (the entry keeps tile_bins alive: its id
+    cannot be recycled while the entry lives)."""
+    oc = S.order_cache
+    oc[(id(tile_bins), int(long_thresh))] = (tile_bins, order)
+    while len(oc) > 4:
+        oc.popitem(last=False)
+
+
 def _order_scratch(S, lib, n_tiles, dev):
-    """The persistent zero-filled scratch of the multi-workgroup tile order (one per stream and tile count)."""
+    """The persistent scratch of the multi-workgroup tile order (one per stream and tile count): zero-filled once, and
+    every launch leaves it zero-filled (include/sgn_rast.h)."""
     if not (tile_order_enabled and tile_order_multiblock):
         return None
     scratch = S.order_scratch.get(n_tiles)
@@ -1593,11 +1581,7 @@ def _forward_window_composite(S, cand, n, xys_c, depths, radii, num_tiles_hit, c
     rows = L.workspace(lib.sgn_raster_workspace_bytes(n_full, 0, ro_ptr), dev)
     arena = L.workspace(lib.sgn_rasterize_window_arena_bytes(n_tiles), dev)
     scratch = _order_scratch(S, lib, n_tiles, dev)
-    if S.side is None:
-        S.side = [torch.empty(4, 8, dtype=torch.int32).pin_memory(), 0]
-    pool = S.side
-    pinned = pool[0][pool[1] % 4]
-    pool[1] += 1
+    pinned = _side_row(S)
     f = [c if c.is_contiguous() else c.contiguous() for c in keep] + [None] * (6 - len(keep))
     if cull:
         f[5] = f[5].reshape(-1)
@@ -1626,14 +1610,32 @@ def _forward_window_composite(S, cand, n, xys_c, depths, radii, num_tiles_hit, c
     else:
         ids_use, bins_use = ids_full, bins_full
         if order_ready is None and tile_order_enabled:
-            oc = S.order_cache
-            oc[(id(bins_full), _fwd_long_thresh(ro, block_width))] = (bins_full, order)
-            while len(oc) > 4:
-                oc.popitem(last=False)
+            _remember_order(S, bins_full, _fwd_long_thresh(ro, block_width), order)
     return matched.value, n_full, num_intersects, ids_use, bins_use, order_ready if order_ready is not None else order, tile_kmax, rows
 
 
 # --------------------------------------------------------------- rasterize
+def _remember_depth(S, key, out_depth, final_Ts, final_idx, tile_kmax, first_pass=True):
+    """Keep a pass's depth channel and per-pixel state to answer a later depth pass over the same binning.  `first_pass`
+    (the plain passes the "auto" policy switched the channel on for): one more accumulated image nobody has asked for
+    yet — after 8 of them the depth passes have stopped coming and "auto" stops accumulating."""
+    S.depth_caches[key] = dict(key=key, D=out_depth, T=final_Ts, idx=final_idx, kmax=tile_kmax)
+    while len(S.depth_caches) > _State.BIN_ENTRIES:
+        S.depth_caches.popitem(last=False)
+    if first_pass:
+        state = S.depth_state
+        state["unused"] += 1
+        if state["unused"] > 8 and depth_channel == "auto":
+            state["want"], state["unused"] = False, 0
+
+
+def _nothing_visible(img_height, img_width, bg_c, f32):
+    """(out_img, final_Ts, final_idx, gaussian_ids_sorted) of a pass whose list is empty: the background everywhere."""
+    i32 = dict(dtype=torch.int32, device=f32["device"])
+    return (torch.ones(img_height, img_width, 3, **f32) * bg_c, torch.ones(img_height, img_width, **f32),
+            torch.zeros(img_height, img_width, **i32), torch.zeros(0, **i32))
+
+
 class _RasterizeGaussians(Function):
     @staticmethod
     def forward(ctx, xys, depths, radii, conics, num_tiles_hit, colors, opacity, img_height, img_width,
@@ -1743,18 +1745,10 @@ class _RasterizeGaussians(Function):
             if num_intersects < 1:
                 recs = None
                 out_depth = None               # never written (no forward ran): the want_depth branch below returns zeros
-                out_img = torch.ones(img_height, img_width, 3, **f32) * bg_c
-                final_Ts = torch.ones(img_height, img_width, **f32)
-                final_idx = torch.zeros(img_height, img_width, dtype=torch.int32, device=dev)
-                gaussian_ids_sorted = torch.zeros(0, dtype=torch.int32, device=dev)
+                out_img, final_Ts, final_idx, gaussian_ids_sorted = _nothing_visible(img_height, img_width, bg_c, f32)
             if accumulate and num_intersects >= 1:      # (the composite serves plain fresh passes only: cacheable)
                 depth_stats["accumulated"] += 1
-                S.depth_caches[key] = dict(key=key, D=out_depth, T=final_Ts, idx=final_idx, kmax=tile_kmax)
-                while len(S.depth_caches) > _State.BIN_ENTRIES:
-                    S.depth_caches.popitem(last=False)
-                _depth_state["unused"] += 1
-                if _depth_state["unused"] > 8 and depth_channel == "auto":   # the depth passes stopped coming
-                    _depth_state["want"], _depth_state["unused"] = False, 0
+                _remember_depth(S, key, out_depth, final_Ts, final_idx, tile_kmax)
             else:
                 S.depth_caches.pop(key, None)  # binned again without the channel: a stale image must not answer later
         else:
@@ -1798,11 +1792,8 @@ class _RasterizeGaussians(Function):
             elif num_intersects < 1:
                 recs = None
                 out_depth = None            # never written (no forward ran): the want_depth branch below returns zeros
-                out_img = torch.ones(img_height, img_width, 3, **f32) * bg_c
-                gaussian_ids_sorted = torch.zeros(0, dtype=torch.int32, device=dev)
+                out_img, final_Ts, final_idx, gaussian_ids_sorted = _nothing_visible(img_height, img_width, bg_c, f32)
                 tile_bins = torch.zeros(tile_bounds[0] * tile_bounds[1], 2, dtype=torch.int32, device=dev)
-                final_Ts = torch.ones(img_height, img_width, **f32)
-                final_idx = torch.zeros(img_height, img_width, dtype=torch.int32, device=dev)
             elif group_split is not None:
                 # the main pass with the two group accumulations riding on it (sgn_raster_fwd_groups): head = ids below the
                 # split, tail = the others.  The smaller group, if small enough, gets its own compacted list: its backward
@@ -1840,9 +1831,7 @@ class _RasterizeGaussians(Function):
                 if accumulate:
                     depth_stats["accumulated"] += 1
                 if depth_cacheable:
-                    S.depth_caches[key] = dict(key=key, D=out_depth, T=final_Ts, idx=final_idx, kmax=tile_kmax)
-                    while len(S.depth_caches) > _State.BIN_ENTRIES:
-                        S.depth_caches.popitem(last=False)
+                    _remember_depth(S, key, out_depth, final_Ts, final_idx, tile_kmax, first_pass=False)
                 elif not hit:
                     S.depth_caches.pop(key, None)
             else:
@@ -1869,12 +1858,7 @@ class _RasterizeGaussians(Function):
                     depth_stats["accumulated"] += 1            # an explicit request on a cached list / an id range: not kept
                 elif accumulate:
                     depth_stats["accumulated"] += 1
-                    S.depth_caches[key] = dict(key=key, D=out_depth, T=final_Ts, idx=final_idx, kmax=tile_kmax)
-                    while len(S.depth_caches) > _State.BIN_ENTRIES:
-                        S.depth_caches.popitem(last=False)
-                    _depth_state["unused"] += 1
-                    if _depth_state["unused"] > 8 and depth_channel == "auto":   # the depth passes stopped coming
-                        _depth_state["want"], _depth_state["unused"] = False, 0
+                    _remember_depth(S, key, out_depth, final_Ts, final_idx, tile_kmax)
                 elif not hit:
                     S.depth_caches.pop(key, None)  # re-binned without the channel: a stale image must not answer later
         # (the sink hears of passes that WILL have a backward only: a forward under no_grad — an evaluation image between
