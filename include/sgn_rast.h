@@ -746,6 +746,57 @@ int sgn_densify_stats(int n, const float *xys_grad /*[n,2]*/, const int32_t *rad
                       float *xys_grad_norm /*[n]*/, float *vis_counts /*[n]*/, float *max_2dsize /*[n]*/,
                       sgn_stream_t stream);
 
+/* THE REFINEMENT ITSELF: SplatfactoModel.refinement_after / split_gaussians / dup_gaussians / cull_gaussians and the
+ * optimiser-state surgery dup_in_optim / remove_from_optim (sgn_splatfacto.py:459-720) in three steps over one
+ * caller-allocated workspace, ws >= sgn_densify_workspace_bytes(n) (depends on n only; 0 for n <= 0), which carries the
+ * per-row flags and per-block offsets from one step to the next.  Decisions, output order and values are those of
+ * sgn_rast.densify.Densifier's torch engine: kept originals in input order, then the children of the kept split parents
+ * sample-major (like .repeat(samps, 1)), then the kept duplicates in input order.  Integer sums in a fixed order, no
+ * atomics: bit-identical results for the same input.  All asynchronous on `stream`; n == 0 returns 0 without a launch.
+ * Return codes: -1 n / n_out out of range (n * (n_split_samples + 2) must fit an int32), -2 n_split_samples outside
+ * [1, 64], -3 a required pointer is NULL (or an output aliases its input), -4 image_dim <= 0 with densify on,
+ * -5 workspace too small, -6 bad tensor table, -7 quats not 16-byte aligned.  csrc/densify.hip.
+ *
+ * sgn_densify_decide: one lane per INPUT Gaussian.  With densify != 0 (:571-612)
+ *     high = (xys_grad_norm / vis_counts) * 0.5 * image_dim > densify_grad_thresh        (x/0 = inf is high, 0/0 is not)
+ *     split = (max exp(log_scales) > densify_size_thresh  [| max_2dsize > split_screen_size]) & high
+ *     dup = (max exp(log_scales') <= densify_size_thresh) & high,  log_scales' = log(exp(log_scales) / 1.6) for a split
+ *           parent (the reference shrinks in place before it looks for duplicates: a Gaussian can be both)
+ * and the cull test of :648-672 as the reference applies it to [old, children, dups]: every split parent goes;
+ * sigmoid(opacity_logits) < cull_alpha_thresh, and with too_big_culls != 0 max exp(log_scales') > cull_scale_thresh
+ * [| max_2dsize > cull_screen_size, new rows carrying max_2dsize = 0], remove a row.  The bracketed screen-size tests
+ * run with screen_size_tests != 0 (step < stop_screen_size_at); densify == 0 is the cull-only refinement after
+ * stop_split_at (xys_grad_norm / vis_counts may be NULL then; max_2dsize may be NULL without the screen-size tests).
+ *
+ * sgn_densify_scan: the exclusive offsets of every block of rows, and totals8 (DEVICE int32[8], read back once by the
+ * host): [0] kept originals, [1] split parents (n_splits: the noise has n_split_samples * n_splits rows), [2] split
+ * parents whose children survive, [3] surviving duplicates — N' = [0] + n_split_samples * [2] + [3] — then the
+ * reference's counters with its multiplicity: [4] high_grads_count, [5] refine_dups_count, [6]
+ * refine_culls_toobigs_count (split parents and new rows included), [7] 0; refine_splits_count = [1].
+ *
+ * sgn_densify_apply: two launches.  The first writes src[n_out] (the input row output row r derives from) and
+ * kind[n_out] (0 a bit-exact copy, -1 a duplicate, 1 + noise row of child k = 1 + k * n_splits + rank of the parent among
+ * all split parents).  The second writes `count` (<= 24) output tensors of n_out rows from their n-row inputs; HOST
+ * arrays of length count: DEVICE pointers inputs[i] / outputs[i] (contiguous fp32, never aliased), row_floats[i] floats
+ * per row and roles[i]: 0 a parameter whose new rows copy their source row; 1 `means` (a child's row is
+ * R(q / |q|) (exp(log_scales) * noise[row]) + mean, R by gsplat's quat_to_rotmat); 2 `log_scales` (children and the
+ * duplicate of a split parent get log(exp(.) / 1.6)); 3 an Adam moment (new rows are zeros).  means / log_scales /
+ * quats are the INPUT parameters [n,3] / [n,3] / [n,4], noise [noise_rows,3] the caller's normal deviates.  Elements
+ * are indexed in 64 bits.  n_out == 0 returns 0 without a launch. */
+size_t sgn_densify_workspace_bytes(int n);
+int sgn_densify_decide(int n, const float *xys_grad_norm /*[n]*/, const float *vis_counts /*[n]*/,
+                       const float *max_2dsize /*[n]*/, const float *log_scales /*[n,3]*/,
+                       const float *opacity_logits /*[n]*/, float densify_grad_thresh, float densify_size_thresh,
+                       float split_screen_size, float cull_alpha_thresh, float cull_scale_thresh,
+                       float cull_screen_size, float image_dim, int n_split_samples, int densify,
+                       int screen_size_tests, int too_big_culls, void *ws, size_t ws_bytes, sgn_stream_t stream);
+int sgn_densify_scan(int n, void *ws, size_t ws_bytes, int32_t *totals8 /*device int32[8]*/, sgn_stream_t stream);
+int sgn_densify_apply(int n, int n_out, int n_split_samples, int64_t noise_rows, const float *means,
+                      const float *log_scales, const float *quats, const float *noise /*[noise_rows,3]*/, int count,
+                      const float *const *inputs, float *const *outputs, const int32_t *row_floats,
+                      const int32_t *roles, int32_t *src /*[n_out]*/, int32_t *kind /*[n_out]*/, const void *ws,
+                      size_t ws_bytes, sgn_stream_t stream);
+
 /* Exact k-nearest neighbours of 3-D points (SplatfactoModel.populate_modules, sgn_splatfacto.py:260-264: the reference's
  * k_nearest_sklearn, :439-457, sklearn NearestNeighbors(k + 1) with the first column dropped).  For every row i of
  * points [n,3] (finite fp32; non-finite input gives unspecified rows, never an out-of-bounds access): dist[i, :] = the k

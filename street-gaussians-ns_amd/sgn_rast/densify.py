@@ -5,8 +5,9 @@ The reference updates ``xys_grad_norm`` / ``vis_counts`` / ``max_2Dsize`` every 
 indexing (``t[mask] = t[mask] + ...``: nonzero + gather + index_put per line, each with a host sync).  :class:`Stats`
 keeps the same three tensors (same names, same values) and updates them with ``sgn_densify_stats``; under data
 parallelism :meth:`Stats.sync` reduces them SUM / SUM / MAX so every replica takes identical split / dup / cull
-decisions in ``refinement_after`` (``:550-646``), which is left to the caller — it is control-plane torch code that
-runs every ``refine_every`` steps.
+decisions in ``refinement_after`` (``:550-646``).  :class:`Densifier` is that refinement, every ``refine_every`` steps:
+plain torch by default, or — ``engine="hip"`` — the same decisions, output layout and optimiser surgery with all
+per-Gaussian work in ``csrc/densify.hip`` (``sgn_densify_decide`` / ``_scan`` / ``_apply``).
 """
 from __future__ import annotations
 
@@ -192,9 +193,17 @@ class Densifier:
 
     def __init__(self, params: Dict[str, torch.Tensor], optimizers: Dict[str, torch.optim.Optimizer],
                  config: DensifyConfig = DensifyConfig(), seed: int = 0, group=None, stats: Optional[Stats] = None,
-                 rng_device=None, split_noise: str = "stream"):
+                 rng_device=None, split_noise: str = "stream", engine: str = "torch"):
         assert set(params) == set(PARAM_NAMES) and set(optimizers) >= set(PARAM_NAMES)
         assert split_noise in ("stream", "hashed")
+        # "torch" (default): the refinement as plain torch on whatever device the parameters live on.  "hip": the same
+        # decisions, output layout and optimiser surgery with all per-Gaussian work in csrc/densify.hip (_refine_hip);
+        # device tensors only, no fallback.
+        if engine not in ("torch", "hip"):
+            raise ValueError(f"Densifier: unknown engine {engine!r} (expected 'torch' or 'hip')")
+        if engine == "hip":
+            L.require_device(*params.values())
+        self.engine = engine
         # "stream" (default) draws the split offsets as the reference does: ONE torch.randn((n_splits * samps, 3)) —
         # which Gaussian gets which sample then depends on every other Gaussian's split decision.  "hashed" gives
         # every Gaussian a persistent 62-bit id (children derive theirs from the parent's) and draws its offsets from
@@ -243,11 +252,10 @@ class Densifier:
         self.params[name] = new_param
 
     # ----------------------------------------------------------------------------------------------------- pieces
-    def _split(self, mask: torch.Tensor, samps: int, step: int) -> Dict[str, torch.Tensor]:
-        """:674-710.  The sample offsets are drawn from a generator seeded identically on every rank."""
-        P = self.params
-        n_splits = int(mask.sum().item())
-        dev = P["means"].device
+    def _split_noise(self, mask: torch.Tensor, n_splits: int, samps: int, step: int) -> torch.Tensor:
+        """The [samps * n_splits, 3] normal deviates of ``split_gaussians`` (:680), sample-major, drawn from a generator
+        seeded identically on every rank; also sets ``_child_ids``.  Both engines draw here, so they see the same numbers."""
+        dev = self.params["means"].device
         rdev = dev if self.rng_device is None else torch.device(self.rng_device)
         if self.split_noise == "hashed":
             pid = self.ids[mask].to(rdev)                                             # [n_splits]
@@ -261,6 +269,12 @@ class Densifier:
             gen.manual_seed((self.seed * 1_000_003 + step) & 0x7FFFFFFFFFFFFFFF)
             centered = torch.randn((samps * n_splits, 3), device=rdev, generator=gen).to(dev)
             self._child_ids = torch.zeros(samps * n_splits, dtype=torch.int64, device=dev)
+        return centered
+
+    def _split(self, mask: torch.Tensor, samps: int, step: int) -> Dict[str, torch.Tensor]:
+        """:674-710."""
+        P = self.params
+        centered = self._split_noise(mask, int(mask.sum().item()), samps, step)
         scaled = torch.exp(P["log_scales"][mask].repeat(samps, 1)) * centered
         q = P["quats"][mask] / P["quats"][mask].norm(dim=-1, keepdim=True)
         from .ops import quat_to_rotmat
@@ -293,6 +307,90 @@ class Densifier:
         self.ids = self.ids[keep]
         return culls
 
+    # ------------------------------------------------------------------------------------------------- HIP engine
+    _ROLES = {"means": 1, "log_scales": 2}          # roles of sgn_densify_apply; every other parameter is 0, a moment 3
+
+    def _refine_hip(self, step: int, densify: bool) -> None:
+        """``_split`` + the ``cat``s + ``_cull`` (``densify``) or ``_cull(step, None)`` alone as sgn_densify_decide /
+        _scan / _apply: the same decisions, rows and order, every tensor written once at its final size, ONE host
+        read (the totals: ``n_splits`` sizes the noise, ``N'`` the outputs).  Leaves ``last_src`` / ``last_kind``
+        (int32 [N']: the input row each output row derives from; 0 copy, -1 duplicate, 1 + noise row for a child)."""
+        import ctypes as C
+        P, c, S, lib = self.params, self.cfg, self.stats, L.load()
+        old = {k: P[k].detach() for k in PARAM_NAMES}
+        stats = [None if t is None else t.detach().float().contiguous()
+                 for t in (S.xys_grad_norm, S.vis_counts, S.max_2Dsize)]
+        dev = L.require_device(*old.values(), *stats)
+        for k, t in old.items():
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"Densifier(engine='hip') needs contiguous fp32 parameters ({k})")
+        n, samps = old["means"].shape[0], int(c.n_split_samples)
+        screen_on = step < c.stop_screen_size_at
+        toobig_on = step > c.refine_every * c.reset_alpha_every
+        dim = S.synced_dim if getattr(S, "synced_dim", None) else max(self.last_size[0], self.last_size[1])
+        ws = L.workspace(lib.sgn_densify_workspace_bytes(n), dev)
+        totals = [0] * 8
+        if n > 0:
+            L.check(lib.sgn_densify_decide(
+                n, L.ptr(stats[0]), L.ptr(stats[1]), L.ptr(stats[2]), L.ptr(old["log_scales"]),
+                L.ptr(old["opacity_logits"]), c.densify_grad_thresh, c.densify_size_thresh, c.split_screen_size,
+                c.cull_alpha_thresh, c.cull_scale_thresh, c.cull_screen_size, float(dim), samps, int(densify),
+                int(screen_on), int(toobig_on), L.ptr(ws), ws.numel(), L.stream_ptr()), "sgn_densify_decide")
+            totals_dev = torch.empty(8, dtype=torch.int32, device=dev)
+            L.check(lib.sgn_densify_scan(n, L.ptr(ws), ws.numel(), L.ptr(totals_dev), L.stream_ptr()),
+                    "sgn_densify_scan")
+            if getattr(self, "_totals_host", None) is None:
+                self._totals_host = torch.empty(8, dtype=torch.int32, pin_memory=True)
+            self._totals_host.copy_(totals_dev, non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()             # the one host read of the refinement
+            totals = self._totals_host.tolist()
+        kept, n_splits, kept_parents, kept_dups, n_high, n_dups, n_toobig = totals[:7]
+        n_out = kept + samps * kept_parents + kept_dups
+        if densify:
+            self.record.update(high_grads_count=n_high, refine_splits_count=n_splits, refine_dups_count=n_dups)
+        if toobig_on:
+            self.record["refine_culls_toobigs_count"] = n_toobig
+        noise = None
+        if densify:
+            split_mask = (ws[:n] & 2) != 0
+            noise = self._split_noise(split_mask, n_splits, samps, step).contiguous()
+        src = torch.empty(n_out, dtype=torch.int32, device=dev)
+        kind = torch.empty(n_out, dtype=torch.int32, device=dev)
+        new, moments, rows = {}, {}, []                   # rows: (input, output, floats per row, role)
+        for name in PARAM_NAMES:
+            t = old[name]
+            new[name] = torch.empty((n_out,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
+            rf = int(t[0].numel()) if n else 0
+            if rf > 0:                                    # (SH degree 0: features_rest has no columns)
+                rows.append((t, new[name], rf, self._ROLES.get(name, 0)))
+            st = self.optimizers[name].state.get(P[name], {})
+            if "exp_avg" in st:
+                ms = [st[k].detach() for k in ("exp_avg", "exp_avg_sq")]
+                L.require_device(*ms)
+                if any(m.dtype != torch.float32 or not m.is_contiguous() or m.shape != t.shape for m in ms):
+                    raise ValueError(f"Densifier(engine='hip') needs contiguous fp32 Adam moments ({name})")
+                moments[name] = [torch.empty_like(new[name]) for _ in ms]
+                if rf > 0:
+                    rows += [(m, o, rf, 3) for m, o in zip(ms, moments[name])]
+        if n > 0 and n_out > 0:
+            cnt = len(rows)
+            L.check(lib.sgn_densify_apply(
+                n, n_out, samps, 0 if noise is None else noise.shape[0], L.ptr(old["means"]), L.ptr(old["log_scales"]),
+                L.ptr(old["quats"]), L.ptr(noise), cnt, (C.c_void_p * cnt)(*[r[0].data_ptr() for r in rows]),
+                (C.c_void_p * cnt)(*[r[1].data_ptr() for r in rows]), (C.c_int32 * cnt)(*[r[2] for r in rows]),
+                (C.c_int32 * cnt)(*[r[3] for r in rows]), L.ptr(src), L.ptr(kind), L.ptr(ws), ws.numel(),
+                L.stream_ptr()), "sgn_densify_apply")
+        for name in PARAM_NAMES:                          # the optimiser surgery, once per parameter
+            it = iter(moments.get(name, ()))
+            self._rebind(name, self._leaf_like(P[name], new[name]), lambda t, it=it: next(it))
+        ids = self.ids[src.long()]
+        if densify:
+            dup_ids = _mix64(ids * 8 + 7 + step) & 0x3FFFFFFFFFFFFFFF
+            child = self._child_ids
+            child_ids = child[(kind - 1).clamp(min=0).long()] if child.numel() else torch.zeros_like(ids)
+            ids = torch.where(kind == 0, ids, torch.where(kind < 0, dup_ids, child_ids))
+        self.ids, self.last_src, self.last_kind = ids, src, kind
+
     # ------------------------------------------------------------------------------------------- refinement_after
     @torch.no_grad()
     def refinement_after(self, step: int) -> bool:
@@ -312,7 +410,11 @@ class Densifier:
         reset_interval = c.reset_alpha_every * c.refine_every
         do_densify = step < c.stop_split_at and step % reset_interval > c.num_train_data + c.refine_every
         deleted = None
-        if do_densify:
+        if self.engine == "hip":
+            if do_densify or (step >= c.stop_split_at and c.continue_cull_post_densification):
+                self._refine_hip(step, do_densify)
+                deleted, P = True, self.params
+        elif do_densify:
             # (view-parallel: the size of the frames that showed this model, agreed between the ranks by Stats.sync)
             dim = S.synced_dim if getattr(S, "synced_dim", None) else max(self.last_size[0], self.last_size[1])
             avg = (S.xys_grad_norm / S.vis_counts) * 0.5 * dim
