@@ -493,6 +493,37 @@ int sgn_raster_fwd_groups(int img_h, int img_w, int n, int64_t n_isect, const in
                           const int32_t *tile_order, int32_t *tile_stats, const float *depths, float *out_depth,
                           int split, int own_group, const int32_t *own_ids, const int32_t *own_bins /*[tiles,2]*/,
                           float *group_state, int32_t *group_stats, const sgn_raster_opts *opts, sgn_stream_t stream);
+/* The LAYERED forward of evaluation renders (no upstream counterpart; forward only): ONE walk of the depth list
+ * composites three layers per pixel — "all" (every entry; colour, the depth channel, T), "head" (ids < split: the scene
+ * graph's background sub-model; colour, T) and "tail" (ids >= split: the objects; colour, T) — where the reference
+ * rasterizes six times (sgn_splatfacto.py:954-994 for the scene, sgn_splatfacto_scene_graph.py:364-372 for the two
+ * sub-model accumulations and, in eval mode, the two sub-model images).  An entry's alpha is evaluated once; each layer it
+ * belongs to runs the single pass's recursion on its own state, in the single pass's operation order, so a layer's image
+ * and final transmittance are BIT-EQUAL to sgn_raster_fwd over that id range, in both exact_exp modes
+ * (tests/test_gpu_layers.py).  Rows, sorted ids (quadrant masks included: opts->ids_qmask), bins and tile order are the
+ * ones sgn_raster_fwd takes; the binning is done once for the whole scene.
+ *   out_img  [3][H,W,3]  C + T * background of all / head / tail      final_Ts [3][H,W]      out_depth [H,W] (all)
+ * own_ids / own_bins (both or neither): the tail layer's own compacted list from sgn_list_window(split, n).  With it the
+ * shared walk ends when the all-layer and the head layer are finished and the tail layer goes on along its own list (a few
+ * objects in front of a saturated background never finish); tiles without a tail entry run a one-layer walk.  An empty
+ * layer (split == 0 or split == n) comes back as T = 1, image = background.
+ * 16x16 tiles only: block_width != 16 returns -12. */
+int sgn_raster_layers_fwd(int img_h, int img_w, int block_width, int n, int64_t n_isect,
+                          const int32_t *gaussian_ids_sorted, const int32_t *tile_bins, const float *xys,
+                          const float *conics, const float *colors, const float *opacities, int opacity_is_logit,
+                          const float *background3, const float *depths, int split, const int32_t *own_ids,
+                          const int32_t *own_bins /*[tiles,2]*/, float *out_img, float *final_Ts, float *out_depth,
+                          void *recs_ws, size_t recs_ws_bytes, int rows_built, const int32_t *tile_order,
+                          const sgn_raster_opts *opts, sgn_stream_t stream);
+/* The per-pixel finish of an evaluation render over the three layers of sgn_raster_layers_fwd, one launch, in the
+ * reference's operation order (sgn_splatfacto.py:968-996 with self.training == False; no fma is formed, so every output
+ * equals the eager torch expression bit for bit):
+ *   acc[l] = 1 - T[l];   rgb[l] = clamp(clamp(img[l], max=1) * acc[l] + sky * (1 - acc[l]), 0, 1) for all and head,
+ *   rgb[tail] = clamp(clamp(img[tail], max=1), 0, 1) (scene_graph.py:371 passes no sky);   depth = acc[all] > 1e-3 ?
+ *   D / acc[all] : 10.   sky [H,W,3] may be NULL (use_sky_sphere = False): no blend on any layer.
+ *   rgb [3][H,W,3], acc [3][H,W], depth [H,W]. */
+int sgn_layers_finish(int img_h, int img_w, const float *layer_img, const float *layer_Ts, const float *depth_channel,
+                      const float *sky, float *rgb, float *acc, float *depth, sgn_stream_t stream);
 /* ONE call per autograd node (round 5; no upstream counterpart: upstream's rasterize_gaussians drives its five `_C`
  * calls from Python).  The whole forward of `rasterize_gaussians` over the full scene: sgn_bin_prepare ->
  * asynchronous read-back of the intersection count -> sgn_raster_build_rows -> SPECULATIVE sgn_bin_intersect (sized by

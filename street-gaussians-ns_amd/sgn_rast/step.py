@@ -163,6 +163,98 @@ def render_fused(P: Dict[str, torch.Tensor], cam: Camera, sh_degree_to_use: int 
     return out
 
 
+def _fused_scene_params(models, idft: torch.Tensor, sh_parts: bool = True):
+    """What the fused front ends take for a scene graph: the raw per-model parameters concatenated, the object id of
+    every row and the Fourier weights padded to the widest model -> (P, object_ids, idft_p)."""
+    from . import fused as F_
+    dev = models[0]["means"].device
+    counts = [m["means"].shape[0] for m in models]
+    cat = lambda key: torch.cat([m[key] for m in models], dim=0)                        # :355-360
+    # the SH coefficients stay UN-concatenated (one pair per sub-model: sgn_sh_fwd_parts); `sh_parts=False` keeps the
+    # round-3 form (torch.cat of features_rest, zero-padded cat of features_dc) for A/B and for the tests
+    if sh_parts and len(models) <= F_.SH_MAX_PARTS:
+        sh_dc, sh_rest = [m["features_dc"] for m in models], [m["features_rest"] for m in models]
+    else:
+        sh_dc, sh_rest = F_.cat_features_dc([m["features_dc"] for m in models]), cat("features_rest")
+    P = dict(means=cat("means"), log_scales=cat("log_scales"), quats=cat("quats"),
+             opacity_logits=cat("opacity_logits"), features_rest=sh_rest, features_dc=sh_dc)
+    object_ids = F_.object_ids_for(counts, dev)       # per layout, built once (no per-step device work)
+    # Fourier weights padded to the widest model: rows beyond a model's own dimension stay zero
+    Fs = [m["features_dc"].shape[1] for m in models]
+    Fmax = max(Fs)
+    mask_key = ("fmask", str(dev), tuple(Fs), Fmax)
+    if mask_key not in _CONST:
+        if len(_CONST) > 64:
+            _CONST.clear()
+        _CONST[mask_key] = (torch.arange(Fmax)[None, :] < torch.tensor(Fs)[:, None]).to(dev, torch.float32)
+    idft_p = torch.zeros(len(models), Fmax, device=dev)
+    fw = min(Fmax, idft.shape[1])
+    idft_p[:, :fw] = idft[:, :fw]
+    idft_p = idft_p * _CONST[mask_key]
+    return P, object_ids, idft_p
+
+
+def _world_scene_params(models, poses: torch.Tensor, idft: torch.Tensor):
+    """The aggregation at the head of ``SplatfactoSceneGraphModel.get_outputs`` (:320-360): object Gaussians moved to
+    the world frame, Fourier features collapsed for the frame, everything concatenated -> (P, world_means, dcs)."""
+    dev = models[0]["means"].device
+    cat = lambda key: torch.cat([m[key] for m in models], dim=0)                        # :355-360
+    world_means, world_quats, dcs = [], [], []
+    # the reference's quat_o2w is a CPU float64 4-vector per object (`torch.from_numpy(quaternion_from_matrix(rot))`,
+    # :412): one small read-back per step here, where the reference runs numpy on the host
+    # (the cache entry HOLDS the pose tensor: while it lives no other tensor can take its address, so "same
+    # data_ptr, same version" really means "same bytes" — keyed on the address alone a freed table's successor at
+    # the same address was served the old quaternions: found in round 4 as a test that failed only in the full suite)
+    pk = ("q_o2w", poses.data_ptr(), poses._version, str(dev))
+    hit = _CONST.get(pk)
+    if hit is None or hit[0] is not poses:
+        if len(_CONST) > 64:
+            _CONST.clear()
+        hit = _CONST[pk] = (poses, poses[:, 12:16].detach().to("cpu", torch.float64))
+    q_o2w = hit[1]
+    for i, m in enumerate(models):
+        Fi = m["features_dc"].shape[1]
+        dcs.append((m["features_dc"] * idft[i][:Fi, None]).sum(dim=1, keepdim=True) if Fi > 1
+                   else m["features_dc"])                                          # :239-247
+        if i == 0:
+            world_means.append(m["means"]); world_quats.append(m["quats"])
+        else:
+            R, t, q = poses[i, :9].reshape(3, 3), poses[i, 9:12], poses[i, 12:16]
+            world_means.append(m["means"] @ R.T + t[None, :])                      # :415
+            world_quats.append(quaternion_multiply(q_o2w[i], m["quats"]))           # :416
+    P = dict(means=torch.cat(world_means), quats=torch.cat(world_quats), features_dc=torch.cat(dcs),
+             opacity_logits=cat("opacity_logits"), features_rest=cat("features_rest"),
+             log_scales=cat("log_scales"))
+    return P, world_means, dcs
+
+
+def _submodel_raster(models, world_means, dcs, out, sub, cam: Camera, sh_degree_to_use: int, block_width: int,
+                     background: torch.Tensor, ops, caller_syncs: bool):
+    """``get_submodel_output`` (:255-303) for the sub-models ``sub`` up to its rasterization -> (rgb, alpha) of the
+    drop-in operator; ``out`` holds the per-model splits of the main projection."""
+    # get_submodel_output (:255-303): per-model tensors are aggregated with torch.cat — the geometry from the
+    # per-model SPLITS of the main projection (copies again), the parameters from the sub-models themselves
+    agg = lambda parts: torch.cat([parts[i] for i in sub], dim=0)               # aggregate_submodel_var :249-253
+    means_s = torch.cat([world_means[i] for i in sub], dim=0)
+    dc_s = torch.cat([dcs[i] for i in sub], dim=0)
+    opac_s = torch.cat([models[i]["opacity_logits"] for i in sub], dim=0)
+    rest_s = torch.cat([models[i]["features_rest"] for i in sub], dim=0)
+    xys_s, depths_s, radii_s = agg(out.xys_parts), agg(out.depths_parts), agg(out.radii_parts)
+    conics_s, nth_s = agg(out.conics_parts), agg(out.num_tiles_hit_parts)
+    colors = torch.cat((dc_s, rest_s), dim=1)                                       # :280
+    viewdirs = means_s.detach() - cam.cam_pos
+    viewdirs = viewdirs / viewdirs.norm(dim=-1, keepdim=True)
+    rgbs = torch.clamp(ops.spherical_harmonics(sh_degree_to_use, viewdirs, colors) + 0.5, min=0.0)  # :285 (unused)
+    # render_gaussian_attrs (:916-967) evaluates the SH again from the colours it is handed
+    viewdirs = means_s.detach() - cam.cam_pos
+    viewdirs = viewdirs / viewdirs.norm(dim=-1, keepdim=True)
+    rgbs = torch.clamp(ops.spherical_harmonics(sh_degree_to_use, viewdirs, colors) + 0.5, min=0.0)  # :939
+    if caller_syncs:
+        assert (out.num_tiles_hit > 0).any()                                         # :944 (self.num_tiles_hit)
+    return ops.rasterize_gaussians(xys_s, depths_s, radii_s, conics_s, nth_s, rgbs, torch.sigmoid(opac_s), cam.height,
+                                   cam.width, block_width, background=background, return_alpha=True)   # :954-967
+
+
 def render_scene_graph(models, poses: torch.Tensor, idft: torch.Tensor, cam: Camera, sh_degree_to_use: int = 3,
                        block_width: int = 16, ops=_hip_ops, fused: bool = False,
                        caller_syncs: bool = True, sh_parts: bool = True, groups: bool = True) -> SimpleNamespace:
@@ -180,27 +272,7 @@ def render_scene_graph(models, poses: torch.Tensor, idft: torch.Tensor, cam: Cam
     cat = lambda key: torch.cat([m[key] for m in models], dim=0)                        # :355-360
     if fused:
         from . import fused as F_
-        # the SH coefficients stay UN-concatenated (one pair per sub-model: sgn_sh_fwd_parts); `sh_parts=False` keeps the
-        # round-3 form (torch.cat of features_rest, zero-padded cat of features_dc) for A/B and for the tests
-        if sh_parts and len(models) <= F_.SH_MAX_PARTS:
-            sh_dc, sh_rest = [m["features_dc"] for m in models], [m["features_rest"] for m in models]
-        else:
-            sh_dc, sh_rest = F_.cat_features_dc([m["features_dc"] for m in models]), cat("features_rest")
-        P = dict(means=cat("means"), log_scales=cat("log_scales"), quats=cat("quats"),
-                 opacity_logits=cat("opacity_logits"), features_rest=sh_rest, features_dc=sh_dc)
-        object_ids = F_.object_ids_for(counts, dev)       # per layout, built once (no per-step device work)
-        # Fourier weights padded to the widest model: rows beyond a model's own dimension stay zero
-        Fs = [m["features_dc"].shape[1] for m in models]
-        Fmax = max(Fs)
-        mask_key = ("fmask", str(dev), tuple(Fs), Fmax)
-        if mask_key not in _CONST:
-            if len(_CONST) > 64:
-                _CONST.clear()
-            _CONST[mask_key] = (torch.arange(Fmax)[None, :] < torch.tensor(Fs)[:, None]).to(dev, torch.float32)
-        idft_p = torch.zeros(len(models), Fmax, device=dev)
-        fw = min(Fmax, idft.shape[1])
-        idft_p[:, :fw] = idft[:, :fw]
-        idft_p = idft_p * _CONST[mask_key]
+        P, object_ids, idft_p = _fused_scene_params(models, idft, sh_parts)
         # `groups`: object_acc / background_acc ride on the main pass's walk (rasterize_gaussians_fused(group_split));
         # False keeps the round-3 form, two more id-range passes, for A/B and for the tests
         out = render_fused(P, cam, sh_degree_to_use, block_width, with_depth=True, object_ids=object_ids,
@@ -210,32 +282,7 @@ def render_scene_graph(models, poses: torch.Tensor, idft: torch.Tensor, cam: Cam
             return out
         opac_arg, raster = P["opacity_logits"], F_.rasterize_gaussians_fused
     else:
-        world_means, world_quats, dcs = [], [], []
-        # the reference's quat_o2w is a CPU float64 4-vector per object (`torch.from_numpy(quaternion_from_matrix(rot))`,
-        # :412): one small read-back per step here, where the reference runs numpy on the host
-        # (the cache entry HOLDS the pose tensor: while it lives no other tensor can take its address, so "same
-        # data_ptr, same version" really means "same bytes" — keyed on the address alone a freed table's successor at
-        # the same address was served the old quaternions: found in round 4 as a test that failed only in the full suite)
-        pk = ("q_o2w", poses.data_ptr(), poses._version, str(dev))
-        hit = _CONST.get(pk)
-        if hit is None or hit[0] is not poses:
-            if len(_CONST) > 64:
-                _CONST.clear()
-            hit = _CONST[pk] = (poses, poses[:, 12:16].detach().to("cpu", torch.float64))
-        q_o2w = hit[1]
-        for i, m in enumerate(models):
-            Fi = m["features_dc"].shape[1]
-            dcs.append((m["features_dc"] * idft[i][:Fi, None]).sum(dim=1, keepdim=True) if Fi > 1
-                       else m["features_dc"])                                          # :239-247
-            if i == 0:
-                world_means.append(m["means"]); world_quats.append(m["quats"])
-            else:
-                R, t, q = poses[i, :9].reshape(3, 3), poses[i, 9:12], poses[i, 12:16]
-                world_means.append(m["means"] @ R.T + t[None, :])                      # :415
-                world_quats.append(quaternion_multiply(q_o2w[i], m["quats"]))           # :416
-        P = dict(means=torch.cat(world_means), quats=torch.cat(world_quats), features_dc=torch.cat(dcs),
-                 opacity_logits=cat("opacity_logits"), features_rest=cat("features_rest"),
-                 log_scales=cat("log_scales"))
+        P, world_means, dcs = _world_scene_params(models, poses, idft)
         out = render(P, cam, sh_degree_to_use, block_width, with_depth=True, ops=ops,   # :363
                      split_counts=counts, caller_syncs=caller_syncs)
         if getattr(out, "empty", False):        # nothing visible: the sub-model passes return their empty outputs too
@@ -254,34 +301,175 @@ def render_scene_graph(models, poses: torch.Tensor, idft: torch.Tensor, cam: Cam
             _, acc = raster(out.xys, out.depths, out.radii, out.conics, out.num_tiles_hit, rgbs, opac_arg, H, W,
                             block_width, background=bg_zero, return_alpha=True, id_range=(lo, hi))
             return acc
-        # get_submodel_output (:255-303): per-model tensors are aggregated with torch.cat — the geometry from the
-        # per-model SPLITS of the main projection (copies again), the parameters from the sub-models themselves
-        sub = range(*which)
-        agg = lambda parts: torch.cat([parts[i] for i in sub], dim=0)               # aggregate_submodel_var :249-253
-        means_s = torch.cat([world_means[i] for i in sub], dim=0)
-        dc_s = torch.cat([dcs[i] for i in sub], dim=0)
-        opac_s = torch.cat([models[i]["opacity_logits"] for i in sub], dim=0)
-        rest_s = torch.cat([models[i]["features_rest"] for i in sub], dim=0)
-        xys_s, depths_s, radii_s = agg(out.xys_parts), agg(out.depths_parts), agg(out.radii_parts)
-        conics_s, nth_s = agg(out.conics_parts), agg(out.num_tiles_hit_parts)
-        colors = torch.cat((dc_s, rest_s), dim=1)                                       # :280
-        viewdirs = means_s.detach() - cam.cam_pos
-        viewdirs = viewdirs / viewdirs.norm(dim=-1, keepdim=True)
-        rgbs = torch.clamp(ops.spherical_harmonics(sh_degree_to_use, viewdirs, colors) + 0.5, min=0.0)  # :285 (unused)
-        # render_gaussian_attrs (:916-967) evaluates the SH again from the colours it is handed
-        viewdirs = means_s.detach() - cam.cam_pos
-        viewdirs = viewdirs / viewdirs.norm(dim=-1, keepdim=True)
-        rgbs = torch.clamp(ops.spherical_harmonics(sh_degree_to_use, viewdirs, colors) + 0.5, min=0.0)  # :939
-        if caller_syncs:
-            assert (out.num_tiles_hit > 0).any()                                         # :944 (self.num_tiles_hit)
-        _, acc = raster(xys_s, depths_s, radii_s, conics_s, nth_s, rgbs, torch.sigmoid(opac_s), H, W, block_width,
-                        background=bg_zero, return_alpha=True)
-        return acc
+        return _submodel_raster(models, world_means, dcs, out, range(*which), cam, sh_degree_to_use, block_width, bg_zero,
+                                ops, caller_syncs)[1]
 
     n_bg = counts[0]
     out.object_acc = submodel_acc(n_bg, sum(counts), (1, len(models)))                   # :364-365
     out.background_acc = submodel_acc(0, n_bg, (0, 1))                                   # :366
     return out
+
+
+def _eval_finish(rgb: torch.Tensor, alpha: torch.Tensor, sky: Optional[torch.Tensor]):
+    """``render_gaussian_attrs`` after its rasterization, eval mode (sgn_splatfacto.py:968-975) -> (rgb, alpha[H,W,1])."""
+    alpha = alpha[..., None]                                                           # :968
+    rgb = torch.clamp(rgb, max=1.0)                                                    # :969
+    if sky is not None:
+        rgb = rgb * alpha + sky * (1 - alpha)                                          # :972
+    return rgb.clamp(0.0, 1.0), alpha                                                  # :974-975 (not self.training)
+
+
+def _eval_nothing_visible(H: int, W: int, background: torch.Tensor, sky: Optional[torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The reference's constant outputs when no Gaussian projects onto the image (sgn_splatfacto.py:878-886)."""
+    dev = background.device
+    out = {"rgb": background.repeat(H, W, 1), "accumulation": torch.zeros(H, W, 1, device=dev),
+           "depth": torch.zeros(H, W, 1, device=dev)}
+    if sky is not None:
+        out["sky"] = sky
+    return out
+
+
+def render_eval(P: Dict[str, torch.Tensor], cam: Camera, background: torch.Tensor, sky: Optional[torch.Tensor] = None,
+                sh_degree: int = 3, block_width: int = 16, fused: bool = True, ops=_hip_ops) -> Dict[str, torch.Tensor]:
+    """``SplatfactoModel.get_outputs`` as ``get_outputs_for_camera`` reaches it: ``self.training == False`` under
+    ``torch.no_grad()`` — the full SH degree whatever the step (sgn_splatfacto.py:937-938), a sky image looked up without
+    jitter (``sky`` [H,W,3], e.g. ``sgn_rast.sky.sky_color(base, ..., jitter=None)``; None: ``use_sky_sphere=False``) and
+    the final ``rgb.clamp(0, 1)`` (:974-975).  Returns the reference's keys: ``rgb`` [H,W,3], ``accumulation`` [H,W,1],
+    ``depth`` [H,W,1] and ``sky`` when given.  ``fused=False`` is the call-site replay on the drop-in operators (or the
+    oracle's, ``ops``); ``fused=True`` the fused front ends with the depth channel riding in the colour pass."""
+    H, W = cam.height, cam.width
+    with torch.no_grad():
+        if fused:
+            out = render_fused(P, cam, sh_degree, block_width, background=background, with_depth=True)
+            if bool(out.radii.sum() == 0):                                             # :878
+                return _eval_nothing_visible(H, W, background, sky)
+        else:
+            out = render(P, cam, sh_degree, block_width, background=background, with_depth=True, ops=ops,
+                         retain_xys_grad=False)
+            if getattr(out, "empty", False):
+                return _eval_nothing_visible(H, W, background, sky)
+        rgb, alpha = _eval_finish(out.rgb, out.alpha, sky)
+        res = {"rgb": rgb, "accumulation": alpha, "depth": out.depth}
+        if sky is not None:
+            res["sky"] = sky                                                           # :998-999
+        return res
+
+
+def render_scene_graph_eval(models, poses: torch.Tensor, idft: torch.Tensor, cam: Camera, background: torch.Tensor,
+                            sky: Optional[torch.Tensor] = None, sh_degree: int = 3, block_width: int = 16,
+                            fused: bool = True, ops=_hip_ops, layered: bool = True) -> Dict[str, torch.Tensor]:
+    """``SplatfactoSceneGraphModel.get_outputs`` in EVAL mode (``self.training == False`` under ``torch.no_grad()``:
+    what the reference's render / eval scripts and the trainer's eval image go through) — :func:`render_eval`'s semantics
+    for the scene, the two sub-model accumulations, and the two decomposition images of
+    ``sgn_splatfacto_scene_graph.py:367-372``.  ``models[0]`` is the background, ``models[i>0]`` the objects annotated at
+    this frame (``poses`` / ``idft`` rows as in :func:`render_scene_graph`); ``sky`` [H,W,3] is the sky image looked up
+    without jitter, or None.  Returns the reference's keys and shapes: ``rgb`` [H,W,3], ``accumulation`` / ``depth`` /
+    ``object_acc`` / ``background_acc`` [H,W,1], ``sky`` when given, ``background_rgb`` (the background over the sky) and
+    ``object_rgb`` (the objects alone, no sky) [H,W,3].
+
+    ``fused=False``: the literal replay — six rasterizations (rgb + alpha, depth, two accumulations, two images), the
+    sub-model tensors aggregated with ``torch.cat`` as ``get_submodel_output`` does, on ``ops`` (the drop-in operators or
+    the CPU oracle's).  ``fused=True``: the fused projection and SH, ONE layered rasterization
+    (:func:`sgn_rast.layers.rasterize_layers`) and one finishing launch.  ``layered=False`` keeps the fused front ends
+    but renders the way the training-side API allows — the main pass with the depth channel and the two group
+    accumulations, two more ``id_range`` colour passes, torch expressions after them — for A/B runs and for the tests: the
+    layered call returns the same bits."""
+    dev = models[0]["means"].device
+    H, W = cam.height, cam.width
+    # "prevent empty object" (:338-339): a model without points takes no part in the frame
+    keep = [i for i, m in enumerate(models) if i == 0 or m["means"].shape[0] > 0]
+    if len(keep) < len(models):
+        models = [models[i] for i in keep]
+        poses, idft = poses[keep], idft[keep]
+    counts = [m["means"].shape[0] for m in models]
+    n_bg, n_all = counts[0], sum(counts)
+    no_objects = len(models) == 1
+    zero1 = lambda: torch.zeros(H, W, 1, device=dev)
+
+    def empty_objects(res):
+        # no object at this frame (:263-267): the accumulation pass returns `empty`, the rgb pass {'rgb': empty,
+        # 'depth': empty} — ONE-channel zeros, and the only case in which `object_depth` exists
+        res["object_acc"], res["object_rgb"], res["object_depth"] = zero1(), zero1(), zero1()
+
+    def nothing_visible():
+        # :878-886 for the scene; the sub-model passes have nothing to composite either: zero layers (T = 1, C = 0)
+        # through the same finish — as render_scene_graph does for its `empty` case
+        res = _eval_nothing_visible(H, W, background, sky)
+        blank = background.repeat(H, W, 1)
+        res["background_acc"] = zero1()
+        res["background_rgb"] = _eval_finish(blank, torch.zeros(H, W, device=dev), sky)[0]
+        if no_objects:
+            empty_objects(res)
+        else:
+            res["object_acc"] = zero1()
+            res["object_rgb"] = _eval_finish(blank, torch.zeros(H, W, device=dev), None)[0]
+        return res
+
+    with torch.no_grad():
+        if fused:
+            from . import fused as F_, layers
+            P, object_ids, idft_p = _fused_scene_params(models, idft)
+            xys, depths, radii, conics, _comp, num_tiles_hit, _cov3d = F_.project_gaussians_fused(
+                P["means"], P["log_scales"], P["quats"], cam.viewmat[:3, :], cam.fx, cam.fy, cam.cx, cam.cy, H, W,
+                block_width, object_ids=object_ids, poses=poses)
+            _hip_ops.prefetch_binning(xys, depths, radii, conics, num_tiles_hit, P["opacity_logits"], H, W, block_width,
+                                      opacity_is_logit=True)
+            rgbs = F_.spherical_harmonics_fused(sh_degree, P["means"], cam.cam_pos, P["features_dc"],
+                                                P["features_rest"], object_ids=object_ids, idft=idft_p, poses=poses)
+            if bool(radii.sum() == 0):                                                 # :878
+                return nothing_visible()
+            if not layered:
+                geo = (xys, depths, radii, conics, num_tiles_hit, rgbs, P["opacity_logits"], H, W, block_width)
+                img_all, alpha, D, acc_h, acc_t = F_.rasterize_gaussians_fused(
+                    *geo, background=background, return_alpha=True, depth_channel=True, group_split=n_bg)
+                part = lambda lo, hi: (F_.rasterize_gaussians_fused(*geo, background=background, return_alpha=True,
+                                                                    id_range=(lo, hi))[0]
+                                       if hi > lo else background.repeat(H, W, 1))
+                rgb, a = _eval_finish(img_all, alpha, sky)
+                res = {"rgb": rgb, "accumulation": a, "depth": torch.where(a > 1e-3, D[..., None] / a, 10)}   # :995
+                if sky is not None:
+                    res["sky"] = sky
+                res["background_acc"] = acc_h[..., None]
+                res["background_rgb"] = _eval_finish(part(0, n_bg), acc_h, sky)[0]
+                if no_objects:
+                    empty_objects(res)
+                else:
+                    res["object_acc"] = acc_t[..., None]
+                    res["object_rgb"] = _eval_finish(part(n_bg, n_all), acc_t, None)[0]
+                return res
+            img, Ts, D = layers.rasterize_layers(xys, depths, radii, conics, num_tiles_hit, rgbs, P["opacity_logits"],
+                                                 H, W, block_width, background, n_bg)
+            rgb3, acc3, depth = layers.finish(img, Ts, D, sky)
+            res = {"rgb": rgb3[0], "accumulation": acc3[0][..., None], "depth": depth[..., None]}
+            if sky is not None:
+                res["sky"] = sky
+            res["background_acc"], res["background_rgb"] = acc3[1][..., None], rgb3[1]
+            if no_objects:
+                empty_objects(res)
+            else:
+                res["object_acc"], res["object_rgb"] = acc3[2][..., None], rgb3[2]
+            return res
+        Pw, world_means, dcs = _world_scene_params(models, poses, idft)
+        out = render(Pw, cam, sh_degree, block_width, background=background, with_depth=True, ops=ops,   # :363
+                     split_counts=counts, retain_xys_grad=False)
+        if getattr(out, "empty", False):
+            return nothing_visible()
+        rgb, alpha = _eval_finish(out.rgb, out.alpha, sky)
+        res = {"rgb": rgb, "accumulation": alpha, "depth": out.depth}
+        if sky is not None:
+            res["sky"] = sky
+        sub = lambda which: _submodel_raster(models, world_means, dcs, out, range(*which), cam, sh_degree, block_width,
+                                             background, ops, True)
+        objects, backgr = (1, len(models)), (0, 1)
+        if not no_objects:
+            res["object_acc"] = sub(objects)[1][..., None]                             # :364-365
+        res["background_acc"] = sub(backgr)[1][..., None]                              # :366
+        res["background_rgb"] = _eval_finish(*sub(backgr), sky)[0]                     # :369-370
+        if no_objects:
+            empty_objects(res)
+        else:
+            res["object_rgb"] = _eval_finish(*sub(objects), None)[0]                   # :371-372
+        return res
 
 
 def loss_weights(cam: Camera, seed: int = 7, device="cpu", dtype=torch.float32):
