@@ -858,6 +858,56 @@ int sgn_cloud_nn(int n_target, const float *target /*[n_target,3]*/, int n_query
                  float *dist /*[n_query]*/, int32_t *idx /*[n_query], may be NULL*/, int64_t *visited /*may be NULL*/,
                  void *ws, size_t ws_bytes, sgn_stream_t stream);
 
+/* LiDAR SEEDING (the reference's scripts/pythons/pcd2colmap_points3D.py:114-235 and extract_object_pts.py:114-273: LiDAR
+ * points coloured from the camera image they project into, sorted into the background cloud and one cloud per tracked
+ * box).  One call pair handles one sweep against one camera and at most SGN_SEED_MAX_BOXES boxes.  HOST arguments:
+ * l2w12 (LiDAR -> world, 3x4 row-major), min_z, `boxes` (n_boxes rows; the caller has applied the reference's 1.1
+ * scale to `half`) and `cam`; they are copied into kernel arguments.  DEVICE: points [n,3] fp32 in the LiDAR frame (rows
+ * may hold NaN), image [height,width,3] uint8.
+ * THE ARITHMETIC IS A CONTRACT, fp32 throughout, no contraction, IEEE division; a float32 restatement reproduces every
+ * output bit for bit (tests/seed_oracle.py):
+ *     pw[r]   = ((L[r][0] x + L[r][1] y) + L[r][2] z) + L[r][3]                      L = l2w12
+ *     live    = no NaN in the row  &  z > min_z (strict)  &  !(|pw.x| > 1e5)
+ *     loc[k]  = (R[0][k] d[0] + R[1][k] d[1]) + R[2][k] d[2],  d = pw - center        R = rot (box -> world)
+ *     inside  = |loc[k]| <= half[k] for k = 0, 1, 2                                   (closed: a face is inside)
+ *     pc      = w2c applied to pw, parenthesised as pw
+ *     fu      = (fx pc.x + cx pc.z) / pc.z,  fv = (fy pc.y + cy pc.z) / pc.z
+ *     visible = pc.z > 0  &  fu, fv finite  &  0 <= trunc(fu) < width  &  0 <= trunc(fv) < height
+ *               (truncation toward zero, decided in floating point: fu in (-1, 0) is column 0, as numpy's astype(int))
+ * sgn_seed_classify writes the per-point verdicts and per-block counts into ws and totals (DEVICE int32[n_boxes + 2], read
+ * back once by the host to size the outputs): [b] rows of box b (live & inside_b & visible), [n_boxes] background rows
+ * (live & visible & inside no box), [n_boxes + 1] live points.  sgn_seed_emit, on the same ws / points / image size,
+ * writes the rows, every segment in input point order: the object rows of box 0, then box 1, ... (a point inside two boxes
+ * has a row in both) as obj_local [obj_rows,3] = loc, obj_rgb [obj_rows,3] = the image's 3 bytes at (trunc(fv),
+ * trunc(fu)), obj_src [obj_rows] = the point's index; the background rows as bg_world = pw, bg_rgb, bg_src.  obj_rows /
+ * bg_rows are the capacities of the arrays (rows past them are not written; 0 with NULL arrays skips that kind).
+ * Integer sums in a fixed order, no atomics: stable and bit-identical from run to run.  Asynchronous on `stream`.
+ * ws >= sgn_seed_workspace_bytes(n, n_boxes) (0 when an argument is out of range).  Return codes: -1 n outside
+ * [1, SGN_SEED_MAX_POINTS]; -2 n_boxes outside [0, SGN_SEED_MAX_BOXES]; -3 width / height outside
+ * [1, SGN_SEED_MAX_IMAGE_DIM]; -4 a required pointer is NULL; -5 workspace too small; -6 obj_rows / bg_rows out of range.
+ * csrc/seed.hip. */
+#define SGN_SEED_MAX_BOXES 64
+#define SGN_SEED_MAX_POINTS (1 << 27)
+#define SGN_SEED_MAX_IMAGE_DIM 16384
+typedef struct sgn_seed_box {
+    float center[3]; /* world */
+    float rot[9];    /* box -> world, 3x3 row-major */
+    float half[3];   /* half extents along the box axes */
+} sgn_seed_box;
+typedef struct sgn_seed_cam {
+    float w2c[12];   /* world -> camera, 3x4 row-major */
+    float fx, fy, cx, cy;
+    int32_t width, height;
+} sgn_seed_cam;
+size_t sgn_seed_workspace_bytes(int n, int n_boxes);
+int sgn_seed_classify(int n, const float *points /*[n,3]*/, const float *l2w12 /*host*/, float min_z, int n_boxes,
+                      const sgn_seed_box *boxes /*host, [n_boxes]*/, const sgn_seed_cam *cam /*host*/, void *ws,
+                      size_t ws_bytes, int32_t *totals /*device int32[n_boxes + 2]*/, sgn_stream_t stream);
+int sgn_seed_emit(int n, const float *points /*[n,3]*/, int n_boxes, const uint8_t *image /*[height,width,3]*/,
+                  int width, int height, const void *ws, size_t ws_bytes, float *obj_local, uint8_t *obj_rgb,
+                  int32_t *obj_src, int64_t obj_rows, float *bg_world, uint8_t *bg_rgb, int32_t *bg_src, int64_t bg_rows,
+                  sgn_stream_t stream);
+
 /* BATCHED VIEWS (no upstream counterpart; gsplat 1.x takes [C] cameras per call).  B = n_views cameras share one image
  * size (img_h, img_w), 16x16 tiles and one set of N Gaussians in the fused front end's raw form (means, log-scales, raw
  * quaternions, opacity logits, features_dc [N,1,3], features_rest [N,k-1,3]; no scene graph).  Row b*N + i of every

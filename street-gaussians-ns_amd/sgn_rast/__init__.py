@@ -4,7 +4,8 @@ Only what the hot path needs: the ctypes binding of libsgnrast.so (``_lib``), th
 surface (``ops``), the fused front ends (``fused``: activations / rigid transform / Fourier DC / sigmoid folded into
 the kernels), the callers either side of the path that SURVEY.md §8f ranks next (``sky``: nvdiffrast cube-map lookup,
 ``loss``: L1 + SSIM, ``optim``: multi-tensor Adam, ``densify``: per-step statistics, ``knn``: k-nearest neighbours for the initial
-scales, ``geometry``: nearest neighbours across two clouds and the LiDAR chamfer metric), the data-parallel helpers
+scales, ``geometry``: nearest neighbours across two clouds and the LiDAR chamfer metric, ``seed``: the seed clouds from LiDAR
+sweeps and the initial parameters), the data-parallel helpers
 (``dp``), the call-site replay used by bench/smoke/tests (``step``) and the deterministic synthetic scenes
 (``scenes``).  Sub-modules are imported on demand; none of them has a CPU fallback.
 """

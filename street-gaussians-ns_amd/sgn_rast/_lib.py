@@ -139,6 +139,9 @@ SIGNATURES = {
     "sgn_knn": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sgn_cloud_nn_workspace_bytes": (_sz, [_i, _i]),
     "sgn_cloud_nn": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sgn_seed_workspace_bytes": (_sz, [_i, _i]),
+    "sgn_seed_classify": (_i, [_i, _vp, _vp, _f, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "sgn_seed_emit": (_i, [_i, _vp, _i, _vp, _i, _i, _vp, _sz, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
 }
 
 _lib = None
@@ -162,6 +165,20 @@ class ViewCam(C.Structure):
     """`sgn_view_cam` of include/sgn_rast.h: one camera of a batched-views call (a host array of these is passed)."""
     _fields_ = [("viewmat", C.c_float * 12), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
                 ("cam_pos", C.c_float * 3)]
+
+
+SEED_MAX_BOXES = 64     # SGN_SEED_MAX_BOXES
+
+
+class SeedBox(C.Structure):
+    """`sgn_seed_box` of include/sgn_rast.h: one oriented box of a seeding call (a host array of these is passed)."""
+    _fields_ = [("center", C.c_float * 3), ("rot", C.c_float * 9), ("half", C.c_float * 3)]
+
+
+class SeedCam(C.Structure):
+    """`sgn_seed_cam` of include/sgn_rast.h: the camera of a seeding call."""
+    _fields_ = [("w2c", C.c_float * 12), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("width", C.c_int32), ("height", C.c_int32)]
 
 
 # The library itself is stateless; the HOST keeps the options: one process-wide default object (library defaults,
