@@ -743,6 +743,20 @@ int sgn_l1_ssim_masked_fwd(int h, int w, const float *pred, const float *gt, con
 int sgn_l1_ssim_masked_bwd(int h, int w, const float *pred, const float *gt, const unsigned char *mask,
                            float clamp_max, const void *ws, const float *gscale2, float *v_pred, sgn_stream_t stream);
 
+/* The same loss with the ground truth as the data set caches it: gt is h*w*3 DEVICE bytes (uint8 [h,w,3], rows at
+ * byte 3 w y, no alignment required), read by the kernels themselves; no float image is materialised.  A byte u stands
+ * for the correctly rounded fp32 quotient u / 255, the value the reference caches (sgn_dataset.py:77,
+ * astype("float32") / 255.0) and get_gt_img forms (sgn_splatfacto.py:1003-1012) -- NOT u * (1.0f / 255): 126 of the
+ * 256 byte values differ in the last bit between the two.  The results are therefore bit for bit those of the masked
+ * entries on that float image.  Everything else is sgn_l1_ssim_masked_fwd/bwd: mask may be NULL, the same out4, the same
+ * ws (>= sgn_l1_ssim_masked_workspace_bytes, pass it to sgn_l1_ssim_gt8_bwd only) and the same return codes (-1 h or
+ * w <= 10, -2 a NULL pred / gt / out4 / ws (backward: gscale2, v_pred), -3 ws_bytes too small), before any launch. */
+int sgn_l1_ssim_gt8_fwd(int h, int w, const float *pred, const unsigned char *gt, const unsigned char *mask,
+                        float data_range, float clamp_max, float ssim_lambda, float *out4, int with_grad, void *ws,
+                        size_t ws_bytes, sgn_stream_t stream);
+int sgn_l1_ssim_gt8_bwd(int h, int w, const float *pred, const unsigned char *gt, const unsigned char *mask,
+                        float clamp_max, const void *ws, const float *gscale2, float *v_pred, sgn_stream_t stream);
+
 /* Accumulation regularisers of the reference's loss dictionary, means over the n_pixels = H*W
  * entries of [H,W,1] accumulation images, one pass each way for both terms (either may be absent):
  *   out2[0] = mean([semantic == sky_value] * accumulation)      sgn_splatfacto.py:1090-1093 (losses["sky_accumulation"]

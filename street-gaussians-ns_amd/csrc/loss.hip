@@ -19,6 +19,14 @@
 // in front of the same two terms): template instantiations of the same kernels that read one mask byte per pixel and
 // work on min(pred, clamp_max) * m and gt * m.  The unmasked instantiations compile to the code they had before the
 // mask existed.  The masked entry points also sum (gt m - pred m)^2 per workgroup: the MSE that PSNR needs.
+//
+// Byte ground truth (the gt8 entry points): instantiations whose `gt` is the data set's uint8 [H,W,3] image as it is
+// cached, dequantised in the kernel to the correctly rounded fp32 quotient u / 255 — the value the reference caches
+// (sgn_dataset.py:77, `astype("float32") / 255.0`) and get_gt_img forms (sgn_splatfacto.py:1003-1012) — so no float
+// image is ever materialised.  NOT u * (1 / 255): 126 of the 256 byte values differ in the last bit.  Everything after
+// the patch load is the float code, and the float instantiations compile to what they were before.
+#include <type_traits>
+
 #include "sgn_common.h"
 
 namespace {
@@ -26,6 +34,14 @@ namespace {
 constexpr int WIN = 11, HALO = WIN - 1, TS = 16, PS = TS + HALO;   // tile 16, patch 26
 
 struct Win { float g[WIN]; };
+
+// A ground-truth element as the fp32 the loss works on: a float as it is, a byte as u / 255 (IEEE division: hipcc's
+// default for `/` on gfx950 is the correctly rounded expansion, and no fast-math flag is set for this library).
+template <typename GT>
+__device__ __forceinline__ float gt_value(GT v) {
+    if constexpr (std::is_same<GT, unsigned char>::value) return __fdiv_rn((float)v, 255.f);
+    else return v;
+}
 
 __device__ __forceinline__ float block_sum(float v, float *lds4) {
 #pragma unroll
@@ -46,10 +62,12 @@ constexpr int ROWS_ = ROWF + 3;       // LDS row stride (odd: 3q + c walks disti
 //         the reference does), so L1 and every SSIM window — also one that straddles the mask edge — see zeros on both
 //         images where m = 0.  The means keep their unmasked denominators (the reference multiplies, then .mean()).
 // MSE:    a third partial per workgroup, the sum of (gt m - pred m)^2 over the tile (partials stride 3 instead of 2).
-template <bool MASKED, bool MSE>
+// GT:     float, or unsigned char for a byte image (rows start at byte 3 W y, at no particular alignment: one byte per
+//         lane, consecutive lanes on consecutive bytes, as the float path does with dwords).
+template <bool MASKED, bool MSE, typename GT = float>
 __global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(int H, int W, Win win, float C1, float C2, float cmax,
                                                           const float *__restrict__ pred,
-                                                          const float *__restrict__ gt,
+                                                          const GT *__restrict__ gt,
                                                           float *__restrict__ partials,
                                                           float *__restrict__ dmaps,
                                                           const unsigned char *__restrict__ mask) {
@@ -66,6 +84,7 @@ __global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(int H, int W, Win win,
         // trip per iteration: s_waitcnt vmcnt(0) after every global_load)
         constexpr int NL = (PS * ROWF + 255) / 256;
         float va[NL], vb[NL];
+        GT vg[NL];
         [[maybe_unused]] unsigned char vm[MASKED ? NL : 1];
 #pragma unroll
         for (int it = 0; it < NL; ++it) {
@@ -75,10 +94,12 @@ __global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(int H, int W, Win win,
             const bool ok = e < PS * ROWF && iy < H && gx < rowlen;
             const size_t idx = (size_t)iy * rowlen + gx;
             va[it] = ok ? fminf(pred[idx], cmax) : 0.f;      // fused torch.clamp(rgb, max=1) (sgn_splatfacto.py:969)
-            vb[it] = ok ? gt[idx] : 0.f;
+            vg[it] = ok ? gt[idx] : (GT)0;
             if constexpr (MASKED)                            // ok: gx < 3W, so the pixel column x0 + j / 3 < W
                 vm[it] = ok ? mask[(size_t)iy * W + x0 + j / 3] : (unsigned char)0;
         }
+#pragma unroll
+        for (int it = 0; it < NL; ++it) vb[it] = gt_value(vg[it]);   // after the last load is issued; 0 / 255 = 0
         if constexpr (MASKED) {
 #pragma unroll
             for (int it = 0; it < NL; ++it) {                 // `* 1.0f` is exact: an all-ones mask changes no bit
@@ -196,10 +217,11 @@ __global__ __launch_bounds__(256) void l1_ssim_reduce_kernel(int nblk, const flo
 // gscale (device, 2 floats): upstream gradients of the two means (d loss / d Ll1, d loss / d ssim)
 // MASKED: the expression is evaluated on x = min(pred, cmax) * m and y = gt * m, as the forward formed them, and
 //         v_pred = m * [pred <= cmax] * (...): an exact 0.0 where m = 0 (there x = y = 0 and torch's sign(0) is 0 too)
-template <bool MASKED>
+// GT:     as in the forward
+template <bool MASKED, typename GT = float>
 __global__ __launch_bounds__(256) void l1_ssim_bwd_kernel(int H, int W, Win win, float cmax,
                                                           const float *__restrict__ pred,
-                                                          const float *__restrict__ gt,
+                                                          const GT *__restrict__ gt,
                                                           const float *__restrict__ dmaps,
                                                           const float *__restrict__ gscale,
                                                           float *__restrict__ v_pred,
@@ -268,7 +290,7 @@ __global__ __launch_bounds__(256) void l1_ssim_bwd_kernel(int H, int W, Win win,
                 b = fmaf(g, hm[1][ty + k][tx], b);
                 d = fmaf(g, hm[2][ty + k][tx], d);
             }
-            const float raw = pred[pix + c], yr = gt[pix + c];
+            const float raw = pred[pix + c], yr = gt_value(gt[pix + c]);
             const float xr = fminf(raw, cmax);
             const float x = MASKED ? xr * mk : xr, y = MASKED ? yr * mk : yr;
             const float df = x - y;
@@ -398,6 +420,57 @@ SGN_EXPORT int sgn_l1_ssim_masked_bwd(int h, int w, const float *pred, const flo
     else
         hipLaunchKernelGGL(l1_ssim_bwd_kernel<false>, grid, dim3(256), 0, s, h, w, win, clamp_max, pred, gt, dmaps, gscale2,
                            v_pred, mask);
+    sgn_timing_end(SGN_T_LOSS_BWD, (void *)s);
+    SGN_LAUNCH_CHECK();
+    return 0;
+}
+
+// The byte-ground-truth entry points: the masked ones with gt as the uint8 [h,w,3] image (mask == NULL: no mask), the
+// same out4, the same workspace (sgn_l1_ssim_masked_workspace_bytes) and the same return codes.
+SGN_EXPORT int sgn_l1_ssim_gt8_fwd(int h, int w, const float *pred, const unsigned char *gt, const unsigned char *mask,
+                                   float data_range, float clamp_max, float ssim_lambda,
+                                   float *out4 /*device: [Ll1, ssim, (1-l) Ll1 + l (1-ssim), mse]*/, int with_grad,
+                                   void *ws, size_t ws_bytes, sgn_stream_t stream) {
+    SGN_ARG_CHECK(h > HALO && w > HALO, -1);
+    SGN_ARG_CHECK(pred && gt && out4 && ws, -2);
+    SGN_ARG_CHECK(ws_bytes >= sgn_l1_ssim_masked_workspace_bytes(h, w, with_grad), -3);
+    hipStream_t s = (hipStream_t)stream;
+    float *partials = (float *)ws;
+    float *dmaps = with_grad ? (float *)((char *)ws + partial_bytes(h, w, 3)) : nullptr;
+    const Win win = make_window(1.5f);
+    const float C1 = (0.01f * data_range) * (0.01f * data_range), C2 = (0.03f * data_range) * (0.03f * data_range);
+    const dim3 grid(sgn_cdiv(w, TS), sgn_cdiv(h, TS));
+    sgn_timing_begin(SGN_T_LOSS_FWD, (void *)s);
+    if (mask)
+        hipLaunchKernelGGL((l1_ssim_fwd_kernel<true, true, unsigned char>), grid, dim3(256), 0, s, h, w, win, C1, C2,
+                           clamp_max, pred, gt, partials, dmaps, mask);
+    else
+        hipLaunchKernelGGL((l1_ssim_fwd_kernel<false, true, unsigned char>), grid, dim3(256), 0, s, h, w, win, C1, C2,
+                           clamp_max, pred, gt, partials, dmaps, mask);
+    hipLaunchKernelGGL(l1_ssim_reduce_kernel<true>, dim3(1), dim3(256), 0, s, (int)(grid.x * grid.y), partials,
+                       1.f / (3.f * (float)h * (float)w), 1.f / (3.f * (float)(h - HALO) * (float)(w - HALO)),
+                       ssim_lambda, out4);
+    sgn_timing_end(SGN_T_LOSS_FWD, (void *)s);
+    SGN_LAUNCH_CHECK();
+    return 0;
+}
+
+SGN_EXPORT int sgn_l1_ssim_gt8_bwd(int h, int w, const float *pred, const unsigned char *gt, const unsigned char *mask,
+                                   float clamp_max, const void *ws, const float *gscale2, float *v_pred,
+                                   sgn_stream_t stream) {
+    SGN_ARG_CHECK(h > HALO && w > HALO, -1);
+    SGN_ARG_CHECK(pred && gt && ws && gscale2 && v_pred, -2);
+    hipStream_t s = (hipStream_t)stream;
+    const float *dmaps = (const float *)((const char *)ws + partial_bytes(h, w, 3));
+    const Win win = make_window(1.5f);
+    const dim3 grid(sgn_cdiv(w, TS), sgn_cdiv(h, TS));
+    sgn_timing_begin(SGN_T_LOSS_BWD, (void *)s);
+    if (mask)
+        hipLaunchKernelGGL((l1_ssim_bwd_kernel<true, unsigned char>), grid, dim3(256), 0, s, h, w, win, clamp_max, pred, gt,
+                           dmaps, gscale2, v_pred, mask);
+    else
+        hipLaunchKernelGGL((l1_ssim_bwd_kernel<false, unsigned char>), grid, dim3(256), 0, s, h, w, win, clamp_max, pred,
+                           gt, dmaps, gscale2, v_pred, mask);
     sgn_timing_end(SGN_T_LOSS_BWD, (void *)s);
     SGN_LAUNCH_CHECK();
     return 0;

@@ -6,9 +6,11 @@ the kernels), the callers either side of the path that SURVEY.md §8f ranks next
 ``loss``: L1 + SSIM, ``optim``: multi-tensor Adam, ``densify``: per-step statistics, ``knn``: k-nearest neighbours for the initial
 scales, ``geometry``: nearest neighbours across two clouds and the LiDAR chamfer metric, ``seed``: the seed clouds from LiDAR
 sweeps and the initial parameters), the data-parallel helpers
-(``dp``), the call-site replay used by bench/smoke/tests (``step``) and the deterministic synthetic scenes
+(``dp``), the ground-truth feed of the training loop (``feed``: the data set as pinned bytes, prefetched a step ahead),
+the call-site replay used by bench/smoke/tests (``step``) and the deterministic synthetic scenes
 (``scenes``).  Sub-modules are imported on demand; none of them has a CPU fallback.
 """
+from .feed import Batch, ImageFeed  # noqa: F401
 from .ops import (  # noqa: F401
     bin_and_sort_gaussians,
     compute_cumulative_intersects,

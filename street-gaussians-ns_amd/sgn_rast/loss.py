@@ -14,6 +14,10 @@ ABI (``sgn_l1_ssim_fwd/bwd``) directly on the rasterizer's HWC image; fails loud
 * ``mask=`` on :func:`l1_ssim` / :func:`photometric_loss` — the batch's boolean pixel mask (``:1081-1083``:
   ``gt_img *= mask; rgb *= mask``) folded into the same two kernels (``sgn_l1_ssim_masked_fwd/bwd``).
 * :func:`image_metrics` — ``(psnr, ssim)`` of the evaluation path (``:1135-1151``), one no-grad forward.
+* ``gt`` of dtype ``torch.uint8`` on all three — the data set's bytes as they are cached (``cache_images_type:
+  "uint8"``), read by the kernels themselves (``sgn_l1_ssim_gt8_fwd/bwd``) as the correctly rounded ``u / 255`` that
+  ``get_gt_img`` (``:1003-1012``) forms: bit for bit the float call on ``gt.float() / 255`` computed on the CPU, with no
+  float image materialised and the byte tensor, a quarter the size, kept for the backward.
 * :class:`SSIM` — ``pytorch_msssim.SSIM`` call shape (``forward(X, Y)`` on [1,3,H,W]) for the import shim; the
   permuted views the reference passes are recognised and used in place (no NCHW copy).
 * :func:`sky_accumulation`, :func:`object_acc_entropy`, :func:`accumulation_losses` — the two accumulation
@@ -47,6 +51,13 @@ def _mask_bytes(mask: torch.Tensor) -> torch.Tensor:
     return m.view(torch.uint8) if m.dtype == torch.bool else m
 
 
+def _check_pred(pred) -> None:
+    """A rendered image is floating point; an integer ``pred`` (a byte image passed on the wrong side) is a
+    ``TypeError`` on the host, not a gradient-less conversion."""
+    if isinstance(pred, torch.Tensor) and not pred.is_floating_point():
+        raise TypeError(f"pred must be a floating-point image, got {pred.dtype} (uint8 is accepted for gt only)")
+
+
 def _check_images(pred, gt):
     if pred.dim() != 3 or pred.shape[-1] != 3 or pred.shape != gt.shape:
         raise ValueError(f"l1_ssim expects two [H,W,3] images, got {tuple(pred.shape)} and {tuple(gt.shape)}")
@@ -57,9 +68,10 @@ def _check_images(pred, gt):
 
 
 def _forward(ctx, pred, gt, data_range, clamp_max, ssim_lambda, mask=None):
-    if mask is not None:
+    if mask is not None or gt.dtype == torch.uint8:      # the byte entries are the masked ones with a nullable mask
         return _forward_masked(ctx, pred, gt, data_range, clamp_max, ssim_lambda, mask,
                                bool(ctx.needs_input_grad[0]))
+    _check_pred(pred)
     L.require_device(pred, gt)
     h, w = _check_images(pred, gt)
     p, g = pred.contiguous().float(), gt.contiguous().float()
@@ -77,22 +89,25 @@ def _forward(ctx, pred, gt, data_range, clamp_max, ssim_lambda, mask=None):
 
 def _forward_masked(ctx, pred, gt, data_range, clamp_max, ssim_lambda, mask, need_grad):
     """The masked entry points: ``out4 = [Ll1, ssim, weighted sum, mse]`` of ``min(pred, clamp_max) * m`` and
-    ``gt * m``; ``mask`` may be ``None`` here (the metrics without a mask).  ``ctx`` None: nothing kept for a backward."""
+    ``gt * m``; ``mask`` may be ``None`` here (the metrics without a mask).  ``ctx`` None: nothing kept for a backward.
+    A ``uint8`` ``gt`` goes to the byte entries as it is (``gt * m`` is then ``(u / 255) * m``)."""
+    _check_pred(pred)
     if pred.dim() == 3 and mask is not None:
         check_mask(mask, pred.shape[0], pred.shape[1])                 # TypeError / ValueError before the device check
     L.require_device(pred, gt, mask)
     h, w = _check_images(pred, gt)
-    p, g = pred.contiguous().float(), gt.contiguous().float()
+    gt8 = gt.dtype == torch.uint8
+    p, g = pred.contiguous().float(), gt.detach().contiguous() if gt8 else gt.contiguous().float()
     m = None if mask is None else _mask_bytes(mask)
     lib = L.load()
     out4 = torch.empty(4, dtype=torch.float32, device=p.device)
     maps = L.workspace(lib.sgn_l1_ssim_masked_workspace_bytes(h, w, int(need_grad)), p.device)
     cmax = float("inf") if clamp_max is None else float(clamp_max)
-    L.check(lib.sgn_l1_ssim_masked_fwd(h, w, L.ptr(p), L.ptr(g), L.ptr(m), float(data_range), cmax, float(ssim_lambda),
-                                       L.ptr(out4), int(need_grad), L.ptr(maps), maps.numel(), L.stream_ptr()),
-            "sgn_l1_ssim_masked_fwd")
+    name = "sgn_l1_ssim_gt8_fwd" if gt8 else "sgn_l1_ssim_masked_fwd"
+    L.check(getattr(lib, name)(h, w, L.ptr(p), L.ptr(g), L.ptr(m), float(data_range), cmax, float(ssim_lambda),
+                               L.ptr(out4), int(need_grad), L.ptr(maps), maps.numel(), L.stream_ptr()), name)
     if ctx is not None:
-        ctx.hw, ctx.cmax, ctx.maps, ctx.masked = (h, w), cmax, maps, True
+        ctx.hw, ctx.cmax, ctx.maps, ctx.masked, ctx.gt8 = (h, w), cmax, maps, True, gt8
         ctx.save_for_backward(p, g, m)
     return out4
 
@@ -102,8 +117,9 @@ def _backward(ctx, gscale):
     if ctx.masked:
         p, g, m = ctx.saved_tensors
         v = torch.empty_like(p)
-        L.check(L.load().sgn_l1_ssim_masked_bwd(h, w, L.ptr(p), L.ptr(g), L.ptr(m), ctx.cmax, L.ptr(ctx.maps),
-                                                L.ptr(gscale), L.ptr(v), L.stream_ptr()), "sgn_l1_ssim_masked_bwd")
+        name = "sgn_l1_ssim_gt8_bwd" if ctx.gt8 else "sgn_l1_ssim_masked_bwd"
+        L.check(getattr(L.load(), name)(h, w, L.ptr(p), L.ptr(g), L.ptr(m), ctx.cmax, L.ptr(ctx.maps), L.ptr(gscale),
+                                        L.ptr(v), L.stream_ptr()), name)
         return v
     p, g = ctx.saved_tensors
     v = torch.empty_like(p)
@@ -156,7 +172,12 @@ def l1_ssim(pred: torch.Tensor, gt: torch.Tensor, data_range: float = 1.0, clamp
     means keep their unmasked denominators (3HW and 3(H-10)(W-10): nothing is normalised by the number of kept
     pixels), SSIM windows that straddle the mask edge see zeros on both images, and the clamp comes before the mask.
     The gradient is an exact 0 at masked pixels; the mask gets none; unlike the reference, neither ``pred`` nor ``gt``
-    is modified.  ``mask=None`` is the unmasked path, unchanged."""
+    is modified.  ``mask=None`` is the unmasked path, unchanged.
+
+    ``gt`` of dtype ``torch.uint8`` is the cached byte image: each byte is read in the kernel as the correctly rounded
+    fp32 ``u / 255`` (not ``u * (1 / 255)``, which differs in the last bit for 126 of the 256 values), so the results are
+    those of ``gt.cpu().float() / 255`` bit for bit, and the bytes are what is saved for the backward.  An integer
+    ``pred`` is a ``TypeError``; any other ``gt`` dtype is converted with ``.float()`` as before."""
     if mask is None:
         return _L1SSIM.apply(pred, gt, data_range, clamp_max)
     return _L1SSIM.apply(pred, gt, data_range, clamp_max, mask)
@@ -165,7 +186,8 @@ def l1_ssim(pred: torch.Tensor, gt: torch.Tensor, data_range: float = 1.0, clamp
 def photometric_loss(pred: torch.Tensor, gt: torch.Tensor, ssim_lambda: float = 0.2, clamp_max=None,
                      mask=None) -> torch.Tensor:
     """``(1 - l) * Ll1 + l * (1 - ssim)`` — the sum of losses["Ll1"] and losses["simloss"] (``:1086-1087``), one
-    forward and one backward kernel plus a single scalar multiply.  ``mask``: see :func:`l1_ssim`."""
+    forward and one backward kernel plus a single scalar multiply.  ``mask`` and a ``uint8`` ``gt``: see
+    :func:`l1_ssim`."""
     if mask is None:
         return _Photometric.apply(pred, gt, ssim_lambda, clamp_max)
     return _Photometric.apply(pred, gt, ssim_lambda, clamp_max, mask)
@@ -181,7 +203,7 @@ def image_metrics(pred: torch.Tensor, gt: torch.Tensor, mask=None, data_range: f
     """``(psnr, ssim)`` of two [H,W,3] images as the reference's evaluation computes them (``:1135-1151``: ``gt *
     mask``, ``rgb * mask``, then ``PeakSignalNoiseRatio(data_range=1.0)`` and ``SSIM``): ``psnr = 10 log10(data_range^2 /
     mse)`` with ``mse`` the mean over all 3HW elements of the masked images (identical images: ``+inf``).  0-dim device
-    tensors without an autograd graph and without a host sync.  ``mask`` as in :func:`l1_ssim`."""
+    tensors without an autograd graph and without a host sync.  ``mask``, ``uint8`` ``gt``: see :func:`l1_ssim`."""
     out4 = _metrics_out4(pred, gt, mask, data_range)
     psnr = 10.0 * torch.log10(float(data_range) ** 2 / out4[3].double())
     return psnr.float(), out4[1]
