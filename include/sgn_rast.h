@@ -757,6 +757,27 @@ int sgn_l1_ssim_gt8_fwd(int h, int w, const float *pred, const unsigned char *gt
 int sgn_l1_ssim_gt8_bwd(int h, int w, const float *pred, const unsigned char *gt, const unsigned char *mask,
                         float clamp_max, const void *ws, const float *gscale2, float *v_pred, sgn_stream_t stream);
 
+/* One pyramid level of a batch's byte ground truth, for the reference's coarse-to-fine schedule (sgn_splatfacto.py:
+ * 766-784, :822-823, :1055-1071: while d = 2 ** max(num_downscales - step // resolution_schedule, 0) > 1 the image is
+ * resized with TF.resize(..., antialias=None) -- plain bilinear, align_corners=False -- and the mask and the semantic map
+ * with InterpolationMode.NEAREST).  One launch reads image (uint8 [h,w,3]) and the optional mask / semantic (uint8 [h,w])
+ * and writes image_out (float32 [oh,ow,3]) and mask_out / semantic_out (uint8 [oh,ow]); all DEVICE pointers, contiguous,
+ * no alignment required, no workspace.  mask and mask_out are both NULL or both non-NULL, and so are semantic and
+ * semantic_out.  The arithmetic contract, fp32 throughout, no FMA, per axis (in -> out):
+ *   scale = (float)in / (float)out                        a true fp32 division
+ *   src   = max(scale * ((float)dst + 0.5f) - 0.5f, 0.0f)
+ *   i0    = min((int)src, in - 1);   i1 = i0 + (i0 < in - 1)
+ *   l1    = src - (float)i0;         l0 = 1.0f - l1
+ *   out   = l0h * (l0w * a + l1w * b) + l1h * (l0w * c + l1w * d)    a, b on row i0h; a, c on column i0w
+ *   a..d  = the correctly rounded (float)u / 255.0f of the four bytes, the quotient sgn_l1_ssim_gt8_fwd forms (NOT
+ *           u * (1.0f / 255))
+ *   mask, semantic: the source byte at min((int)floorf((float)dst * scale), in - 1) per axis, unchanged
+ * Return codes, before any device work: -1 a dimension < 1 or > 16384, or oh > h, or ow > w; -2 a NULL image or
+ * image_out, or a mask or semantic pair of which only one is given. */
+int sgn_gt_downscale(int h, int w, int oh, int ow, const unsigned char *image, const unsigned char *mask,
+                     const unsigned char *semantic, float *image_out, unsigned char *mask_out,
+                     unsigned char *semantic_out, sgn_stream_t stream);
+
 /* Accumulation regularisers of the reference's loss dictionary, means over the n_pixels = H*W
  * entries of [H,W,1] accumulation images, one pass each way for both terms (either may be absent):
  *   out2[0] = mean([semantic == sky_value] * accumulation)      sgn_splatfacto.py:1090-1093 (losses["sky_accumulation"]

@@ -684,6 +684,20 @@ int sgn_rasterize_views_bwd_all(int n_views, int n, int64_t n_isect, int img_h, 
                                 stream, aux_stream);
 }
 
+// ---------------------------------------------------------------- the ground-truth pyramid (gt_pyramid.hip)
+SGN_EXPORT
+int sgn_gt_downscale(int h, int w, int oh, int ow, const unsigned char *image, const unsigned char *mask,
+                     const unsigned char *semantic, float *image_out, unsigned char *mask_out,
+                     unsigned char *semantic_out, sgn_stream_t stream) {
+    constexpr int MAX_DIM = 16384;                     // 32-bit element indices: 16384 * 16384 * 3 < 2^31
+    SGN_ARG_CHECK(h >= 1 && w >= 1 && oh >= 1 && ow >= 1 && h <= MAX_DIM && w <= MAX_DIM, -1);
+    SGN_ARG_CHECK(oh <= h && ow <= w, -1);
+    SGN_ARG_CHECK(image && image_out, -2);
+    SGN_ARG_CHECK((mask != nullptr) == (mask_out != nullptr), -2);
+    SGN_ARG_CHECK((semantic != nullptr) == (semantic_out != nullptr), -2);
+    return sgn_gt_downscale_launch(h, w, oh, ow, image, mask, semantic, image_out, mask_out, semantic_out, stream);
+}
+
 // ---------------------------------------------------------------- kernel timing (bench/profiles)
 // Opt-in: when enabled every timed launch is bracketed by hipEventRecord on the SAME stream the
 // kernel is launched on; sgn_timing_get() synchronises the recorded events and sums them.

@@ -39,7 +39,7 @@ struct Win { float g[WIN]; };
 // default for `/` on gfx950 is the correctly rounded expansion, and no fast-math flag is set for this library).
 template <typename GT>
 __device__ __forceinline__ float gt_value(GT v) {
-    if constexpr (std::is_same<GT, unsigned char>::value) return __fdiv_rn((float)v, 255.f);
+    if constexpr (std::is_same<GT, unsigned char>::value) return sgn_byte_unorm(v);
     else return v;
 }
 

@@ -93,6 +93,12 @@ int sgn_raster_views_bwd(int n_views, int n, int img_h, int img_w, const int32_t
                          float *v_opacity, void *grad_ws, const int32_t *tile_order, const sgn_raster_opts *opts,
                          sgn_stream_t stream, sgn_stream_t aux_stream);
 
+// gt_pyramid.hip: the launch behind sgn_gt_downscale (api.cpp checks the arguments); the two fp32 quotients in / out are
+// formed on the host and travel as kernel arguments
+int sgn_gt_downscale_launch(int h, int w, int oh, int ow, const unsigned char *image, const unsigned char *mask,
+                            const unsigned char *semantic, float *image_out, unsigned char *mask_out,
+                            unsigned char *semantic_out, sgn_stream_t stream);
+
 // Batched views (include/sgn_rast.h "Batched views"): the camera table travels BY VALUE as a kernel argument (SGPRs /
 // the kernarg segment, no device buffer, no copy), one entry per view; the host fills it from sgn_view_cam rows.
 struct SgnViews {
@@ -124,6 +130,11 @@ static inline SgnViews sgn_views_table(int n_views, const sgn_view_cam *cams, in
 }
 
 static inline int sgn_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// A byte of a cached uint8 image as the fp32 it stands for: the correctly rounded quotient u / 255 (IEEE division, NOT
+// u * (1 / 255): 126 of the 256 byte values differ in the last bit).  Shared by the byte loss (loss.hip) and the
+// ground-truth pyramid (gt_pyramid.hip), which therefore form the same number.
+__device__ __forceinline__ float sgn_byte_unorm(unsigned char u) { return __fdiv_rn((float)u, 255.f); }
 
 // float -> int with v_cvt_i32_f32 semantics (saturating, NaN -> 0); the C oracle spells the
 // same rule out (oracle/c/sgn_oracle.c f2i).

@@ -6,7 +6,8 @@ the kernels), the callers either side of the path that SURVEY.md §8f ranks next
 ``loss``: L1 + SSIM, ``optim``: multi-tensor Adam, ``densify``: per-step statistics, ``knn``: k-nearest neighbours for the initial
 scales, ``geometry``: nearest neighbours across two clouds and the LiDAR chamfer metric, ``seed``: the seed clouds from LiDAR
 sweeps and the initial parameters), the data-parallel helpers
-(``dp``), the ground-truth feed of the training loop (``feed``: the data set as pinned bytes, prefetched a step ahead),
+(``dp``), the ground-truth feed of the training loop (``feed``: the data set as pinned bytes, prefetched a step ahead), the
+coarse-to-fine resolution schedule on those bytes (``pyramid``: one level of a batch's ground truth in one launch),
 the call-site replay used by bench/smoke/tests (``step``) and the deterministic synthetic scenes
 (``scenes``).  Sub-modules are imported on demand; none of them has a CPU fallback.
 """
@@ -23,5 +24,6 @@ from .ops import (  # noqa: F401
     set_alpha_clamp_bwd,
     spherical_harmonics,
 )
+from .pyramid import Level, downscale, downscale_factor, level_size, scaled_camera  # noqa: F401
 
 __version__ = "0.1.0"

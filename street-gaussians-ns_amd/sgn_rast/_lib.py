@@ -58,6 +58,7 @@ SIGNATURES = {
     "sgn_l1_ssim_masked_bwd": (_i, [_i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
     "sgn_l1_ssim_gt8_fwd": (_i, [_i, _i, _vp, _vp, _vp, _f, _f, _f, _vp, _i, _vp, _sz, _vp]),
     "sgn_l1_ssim_gt8_bwd": (_i, [_i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
+    "sgn_gt_downscale": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sgn_acc_losses_workspace_bytes": (_sz, [_i64]),
     "sgn_acc_losses_fwd": (_i, [_i64, _vp, _vp, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
     "sgn_acc_losses_bwd": (_i, [_i64, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
