@@ -778,6 +778,46 @@ int sgn_gt_downscale(int h, int w, int oh, int ow, const unsigned char *image, c
                      const unsigned char *semantic, float *image_out, unsigned char *mask_out,
                      unsigned char *semantic_out, sgn_stream_t stream);
 
+/* A frame's eval outputs as the bytes an image or video writer takes (the reference's scripts/render.py:159-273 runs every
+ * output of every frame through colormaps.apply_colormap / apply_depth_colormap, moves the float32 result to the host
+ * and leaves the float -> uint8 conversion to the writer; sgn_splatfacto.py:1134 builds the trainer's eval image the same
+ * way).  One launch packs n_panels panels (1..SGN_FRAMES_MAX_PANELS), all h x w, into canvas, uint8
+ * [canvas_h, canvas_w, 3]: panel i covers rows y0 .. y0 + h - 1 and columns x0 .. x0 + w - 1, so one call makes a column
+ * of separate images or a side-by-side mosaic.  `panels` is a HOST array; it is copied into the kernel arguments (no
+ * device buffer, no copy, no workspace, no host synchronisation).  src, lut and canvas are DEVICE pointers, contiguous,
+ * no alignment required (16-byte aligned float sources, 4-byte aligned byte sources and canvas, with w, x0 and canvas_w
+ * multiples of 4, take the 16-bytes-per-lane path; everything else goes byte by byte and returns the same bytes).
+ * The rectangles must lie inside the canvas and must not overlap; bytes of the canvas outside them are not written.
+ * THE ARITHMETIC IS A CONTRACT (tests/frames_oracle.py restates it), fp32, every operation rounded on its own:
+ *   unit(v) = v > 0 ? (v < 1 ? v : 1) : 0                       clamp to [0, 1]; NaN -> 0, -inf -> 0, +inf -> 1
+ *   q(x)    = (uint8) trunc(unit(x) * 255.0f + 0.5f)            the writers' float -> uint8 conversion (as recalled:
+ *                                                               unpinned, no writer library was at hand)
+ *   SGN_PANEL_RGB     src float32 [h,w,3]; each channel through q (apply_colormap returns 3-channel images unchanged)
+ *   SGN_PANEL_SCALAR  src float32 [h,w];   t = (x - lo) / den   an IEEE fp32 division, not a reciprocal multiply
+ *                                          t = clip(t, 0, 1), NaN propagating; then NaN -> 0      [together: unit(t)]
+ *                                          t = 1 - t            if invert
+ *                                          the pixel's three bytes are lut[(int) trunc(t * 255.0f)], lut uint8 [256,3]
+ *                     lo = 0, den = 1 is apply_colormap's default path for accumulations (x * (1 - 0) + 0 is x); depth
+ *                     takes lo = near and den = (float)((double)far - (double)near + 1e-10) (apply_depth_colormap)
+ *   SGN_PANEL_BYTES   src uint8 [h,w,3], copied (the ground truth of a feed batch)
+ * Return codes, before any device work: -1 h, w, canvas_h or canvas_w outside [1, 16384], n_panels outside
+ * [1, SGN_FRAMES_MAX_PANELS], an unknown kind, a rectangle that leaves the canvas, two rectangles that overlap, a SCALAR
+ * panel's den zero or not finite; -2 a NULL panels, canvas, src, or SCALAR panel's lut.  csrc/frame_pack.hip. */
+#define SGN_FRAMES_MAX_PANELS 16
+#define SGN_PANEL_RGB 0
+#define SGN_PANEL_SCALAR 1
+#define SGN_PANEL_BYTES 2
+typedef struct sgn_panel {
+    const void *src;    /* device: float32 [h,w,3] (RGB), float32 [h,w] (SCALAR), uint8 [h,w,3] (BYTES) */
+    const uint8_t *lut; /* device: uint8 [256,3], SCALAR only (ignored otherwise) */
+    int32_t kind;       /* SGN_PANEL_* */
+    int32_t y0, x0;     /* top-left corner on the canvas */
+    int32_t invert;     /* SCALAR: non-zero = t -> 1 - t */
+    float lo, den;      /* SCALAR: t = (x - lo) / den */
+} sgn_panel;
+int sgn_frames_pack(int h, int w, int n_panels, const sgn_panel *panels /*host, [n_panels]*/, uint8_t *canvas,
+                    int canvas_h, int canvas_w, sgn_stream_t stream);
+
 /* Accumulation regularisers of the reference's loss dictionary, means over the n_pixels = H*W
  * entries of [H,W,1] accumulation images, one pass each way for both terms (either may be absent):
  *   out2[0] = mean([semantic == sky_value] * accumulation)      sgn_splatfacto.py:1090-1093 (losses["sky_accumulation"]

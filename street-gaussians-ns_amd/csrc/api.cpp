@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <mutex>
 #include <vector>
 
@@ -696,6 +697,33 @@ int sgn_gt_downscale(int h, int w, int oh, int ow, const unsigned char *image, c
     SGN_ARG_CHECK((mask != nullptr) == (mask_out != nullptr), -2);
     SGN_ARG_CHECK((semantic != nullptr) == (semantic_out != nullptr), -2);
     return sgn_gt_downscale_launch(h, w, oh, ow, image, mask, semantic, image_out, mask_out, semantic_out, stream);
+}
+
+// ---------------------------------------------------------------- eval outputs as writer bytes (frame_pack.hip)
+SGN_EXPORT
+int sgn_frames_pack(int h, int w, int n_panels, const sgn_panel *panels, uint8_t *canvas, int canvas_h, int canvas_w,
+                    sgn_stream_t stream) {
+    constexpr int MAX_DIM = 16384;                     // 32-bit element indices: 16384 * 16384 * 3 < 2^31
+    SGN_ARG_CHECK(h >= 1 && w >= 1 && canvas_h >= 1 && canvas_w >= 1, -1);
+    SGN_ARG_CHECK(h <= MAX_DIM && w <= MAX_DIM && canvas_h <= MAX_DIM && canvas_w <= MAX_DIM, -1);
+    SGN_ARG_CHECK(n_panels >= 1 && n_panels <= SGN_FRAMES_MAX_PANELS, -1);
+    SGN_ARG_CHECK(panels && canvas, -2);
+    for (int i = 0; i < n_panels; ++i) {
+        const sgn_panel &p = panels[i];
+        SGN_ARG_CHECK(p.kind == SGN_PANEL_RGB || p.kind == SGN_PANEL_SCALAR || p.kind == SGN_PANEL_BYTES, -1);
+        SGN_ARG_CHECK(p.y0 >= 0 && p.x0 >= 0 && p.y0 <= canvas_h - h && p.x0 <= canvas_w - w, -1);
+        SGN_ARG_CHECK(p.kind != SGN_PANEL_SCALAR || (std::isfinite(p.den) && p.den != 0.0f), -1);
+        for (int j = 0; j < i; ++j) {
+            const sgn_panel &o = panels[j];
+            const bool panels_do_not_overlap = p.y0 >= o.y0 + h || o.y0 >= p.y0 + h || p.x0 >= o.x0 + w || o.x0 >= p.x0 + w;
+            SGN_ARG_CHECK(panels_do_not_overlap, -1);
+        }
+    }
+    for (int i = 0; i < n_panels; ++i) {
+        SGN_ARG_CHECK(panels[i].src, -2);
+        SGN_ARG_CHECK(panels[i].kind != SGN_PANEL_SCALAR || panels[i].lut, -2);
+    }
+    return sgn_frames_pack_launch(h, w, n_panels, panels, canvas, canvas_w, stream);
 }
 
 // ---------------------------------------------------------------- kernel timing (bench/profiles)

@@ -99,6 +99,11 @@ int sgn_gt_downscale_launch(int h, int w, int oh, int ow, const unsigned char *i
                             const unsigned char *semantic, float *image_out, unsigned char *mask_out,
                             unsigned char *semantic_out, sgn_stream_t stream);
 
+// frame_pack.hip: the launch behind sgn_frames_pack (api.cpp checks the arguments); the panel table is copied into the
+// kernel arguments
+int sgn_frames_pack_launch(int h, int w, int n_panels, const sgn_panel *panels, unsigned char *canvas, int canvas_w,
+                           sgn_stream_t stream);
+
 // Batched views (include/sgn_rast.h "Batched views"): the camera table travels BY VALUE as a kernel argument (SGPRs /
 // the kernarg segment, no device buffer, no copy), one entry per view; the host fills it from sgn_view_cam rows.
 struct SgnViews {

@@ -59,6 +59,7 @@ SIGNATURES = {
     "sgn_l1_ssim_gt8_fwd": (_i, [_i, _i, _vp, _vp, _vp, _f, _f, _f, _vp, _i, _vp, _sz, _vp]),
     "sgn_l1_ssim_gt8_bwd": (_i, [_i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
     "sgn_gt_downscale": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sgn_frames_pack": (_i, [_i, _i, _i, _vp, _vp, _i, _i, _vp]),
     "sgn_acc_losses_workspace_bytes": (_sz, [_i64]),
     "sgn_acc_losses_fwd": (_i, [_i64, _vp, _vp, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
     "sgn_acc_losses_bwd": (_i, [_i64, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
@@ -182,6 +183,16 @@ class SeedCam(C.Structure):
     """`sgn_seed_cam` of include/sgn_rast.h: the camera of a seeding call."""
     _fields_ = [("w2c", C.c_float * 12), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
                 ("width", C.c_int32), ("height", C.c_int32)]
+
+
+FRAMES_MAX_PANELS = 16      # SGN_FRAMES_MAX_PANELS
+PANEL_RGB, PANEL_SCALAR, PANEL_BYTES = 0, 1, 2      # SGN_PANEL_*
+
+
+class PanelDesc(C.Structure):
+    """`sgn_panel` of include/sgn_rast.h: one panel of a frame-packing call (a host array of these is passed)."""
+    _fields_ = [("src", C.c_void_p), ("lut", C.c_void_p), ("kind", C.c_int32), ("y0", C.c_int32), ("x0", C.c_int32),
+                ("invert", C.c_int32), ("lo", C.c_float), ("den", C.c_float)]
 
 
 # The library itself is stateless; the HOST keeps the options: one process-wide default object (library defaults,
