@@ -11,6 +11,12 @@
 // lane walks its own K*3 row from LDS; the row stride (3K+1 dwords) is odd, so the 64 lanes hit
 // distinct banks.  The backward writes v_coeffs the same way in reverse (row -> LDS -> coalesced
 // dwordx4 stores).
+//
+// Five kernel families (plain, fused front end, un-concatenated sub-models, multi-view backward, batched views) share
+// the per-row helpers below: the families that promise each other equal bits run the same source operations in the
+// same order (-ffp-contract=off), because they call the same code.
+#include <type_traits>
+
 #include "sgn_common.h"
 
 namespace {
@@ -52,60 +58,15 @@ __device__ __forceinline__ int sh_bases(float dx, float dy, float dz, int deg, f
     return 25;
 }
 
-// Copy this wave's `cnt` contiguous coefficient rows (KC floats each, 16-byte aligned span) into its LDS slab with
-// row stride LS.  ALL global loads are issued before the first LDS write: written as a plain `for (t...) { load;
-// store }` loop the compiler emits load -> s_waitcnt vmcnt(0) -> ds_write per iteration, i.e. 12 serialised HBM
-// round trips per wave (sh_fwd: 68 us -> see DESIGN.md).
-template <int KC, int LS>
-__device__ __forceinline__ void stage_rows(float *__restrict__ my, const float *__restrict__ src, int cnt, int lane) {
-    constexpr int NIT = (16 * KC + 63) / 64;          // float4 loads per lane for a full wave of 64 rows
-    const int total = cnt * KC;
-    if (reinterpret_cast<uintptr_t>(src) & 15) {      // a view with an odd storage offset: plain dword copy
-        for (int e = lane; e < total; e += 64) {
-            const int r = e / KC, c = e - r * KC;
-            my[r * LS + c] = src[e];
-        }
-        return;
-    }
-    const int n4 = total >> 2;
-    const float4 *src4 = reinterpret_cast<const float4 *>(src);
-    float4 v[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int t = lane + 64 * it;
-        v[it] = (t < n4) ? src4[t] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int t = lane + 64 * it;
-        if (t < n4) {
-            const float f[4] = {v[it].x, v[it].y, v[it].z, v[it].w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int e = 4 * t + j, r = e / KC, c = e - r * KC;
-                my[r * LS + c] = f[j];
-            }
-        }
-    }
-    const int e = (n4 << 2) + lane;                   // up to three trailing floats of a partial wave
-    if (lane < (total & 3)) {
-        const int r = e / KC, c = e - r * KC;
-        my[r * LS + c] = src[e];
-    }
-}
-
-// LDS traffic between lanes of ONE wave (private slab): the hardware retires a wave's LDS operations in order, the
-// fence only keeps the compiler from moving them across
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// stage_rows split in two, so that the loads of the NEXT span can be in flight while this one is evaluated
+// ---- stage-in: a wave's contiguous coefficient rows -> its LDS slab --------------------------------------------------
+// The two halves of the aligned copy, separate so that the loads of the NEXT span can be in flight while this one is
+// evaluated (sh_fwd_kernel).  ALL global loads are issued before the first LDS write: written as a plain
+// `for (t...) { load; store }` loop the compiler emits load -> s_waitcnt vmcnt(0) -> ds_write per iteration, i.e. 12
+// serialised HBM round trips per wave (sh_fwd: 68 us -> see DESIGN.md).
 template <int KC>
 __device__ __forceinline__ void load_span(float4 (&v)[(16 * KC + 63) / 64], const float *__restrict__ src, int cnt,
                                           int lane) {
-    constexpr int NIT = (16 * KC + 63) / 64;
+    constexpr int NIT = (16 * KC + 63) / 64;          // float4 loads per lane for a full wave of 64 rows
     const int n4 = (cnt * KC) >> 2;
     const float4 *src4 = reinterpret_cast<const float4 *>(src);
 #pragma unroll
@@ -138,6 +99,141 @@ __device__ __forceinline__ void store_span(float *__restrict__ my, const float4 
     }
 }
 
+// Copy this wave's `cnt` contiguous coefficient rows (KC floats each) into its LDS slab with row stride LS.
+template <int KC, int LS>
+__device__ __forceinline__ void stage_rows(float *__restrict__ my, const float *__restrict__ src, int cnt, int lane) {
+    const int total = cnt * KC;
+    if (reinterpret_cast<uintptr_t>(src) & 15) {      // a view with an odd storage offset: plain dword copy
+        for (int e = lane; e < total; e += 64) {
+            const int r = e / KC, c = e - r * KC;
+            my[r * LS + c] = src[e];
+        }
+        return;
+    }
+    float4 v[(16 * KC + 63) / 64];
+    load_span<KC>(v, src, cnt, lane);
+    store_span<KC, LS>(my, v, src, cnt, lane);
+}
+
+// LDS traffic between lanes of ONE wave (private slab): the hardware retires a wave's LDS operations in order, the
+// fence only keeps the compiler from moving them across
+__device__ __forceinline__ void wave_lds_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// ---- drain: the wave's LDS rows -> `cnt` contiguous global rows of W floats -----------------------------------------
+// Row r of the slab starts at my + r * LS; its columns C0 .. C0 + W - 1 go out.  VEC4 (W % 4 == 0 and a 16-byte
+// aligned dst) stores float4, otherwise one dword per lane.
+template <int W, int LS, int C0, bool VEC4>
+__device__ __forceinline__ void drain_rows(float *dst, const float *my, int cnt, int lane) {
+    const int total = cnt * W;
+    if constexpr (VEC4) {
+        float4 *dst4 = reinterpret_cast<float4 *>(dst);
+        for (int t = lane; t < total / 4; t += 64) {
+            const int e = t * 4, r = e / W, c = e - r * W;
+            const float *s = my + r * LS + C0 + c;
+            dst4[t] = make_float4(s[0], s[1], s[2], s[3]);
+        }
+    } else {
+        for (int e = lane; e < total; e += 64) {
+            const int r = e / W, c = e - r * W;
+            dst[e] = my[r * LS + C0 + c];
+        }
+    }
+}
+// Rows of KC floats, split over the two leaves of the reference: band 0 -> v_dc [n,3], the rest -> v_rest [n,K-1,3].
+template <int KC, int LS>
+__device__ __forceinline__ void drain_dc_rest(float *v_dc, float *v_rest, int g0, const float *my, int cnt, int lane) {
+    drain_rows<3, LS, 0, false>(v_dc + (size_t)g0 * 3, my, cnt, lane);
+    if constexpr (KC > 3) drain_rows<KC - 3, LS, 3, false>(v_rest + (size_t)g0 * (KC - 3), my, cnt, lane);
+}
+
+// ---- per-row arithmetic ---------------------------------------------------------------------------------------------
+// local -> world by one 16-float pose row (scene_graph.py:414)
+__device__ __forceinline__ void pose_apply(const float *P, float &m0, float &m1, float &m2) {
+    const float w0 = P[0] * m0 + P[1] * m1 + P[2] * m2 + P[9];
+    const float w1 = P[3] * m0 + P[4] * m1 + P[5] * m2 + P[10];
+    const float w2 = P[6] * m0 + P[7] * m1 + P[8] * m2 + P[11];
+    m0 = w0; m1 = w1; m2 = w2;
+}
+
+__device__ __forceinline__ void fused_viewdir(int i, const float *__restrict__ means,
+                                              const float *__restrict__ cam_pos,
+                                              const int32_t *__restrict__ object_ids,
+                                              const float *__restrict__ poses, float &dx, float &dy, float &dz) {
+    float m0 = means[3 * i], m1 = means[3 * i + 1], m2 = means[3 * i + 2];
+    if (poses != nullptr && object_ids != nullptr) pose_apply(poses + 16 * (size_t)object_ids[i], m0, m1, m2);
+    dx = m0 - cam_pos[0]; dy = m1 - cam_pos[1]; dz = m2 - cam_pos[2];
+}
+
+// Effective DC term of one row, dc_eff = sum_f dc[f, :] * w[f] from 0.f in ascending f (Fourier "4D-SH" DC term,
+// sgn_splatfacto_scene_graph.py:239-247).  `w` is anything indexable; the batched views pass ShUnitWeight with F = 1,
+// which performs 0.f + dc * 1.f and NOT just `dc`: the sum turns a -0.f into +0.f, as the fused kernel's does.
+struct ShUnitWeight {
+    __device__ __forceinline__ float operator[](int) const { return 1.f; }
+};
+template <class Weights>
+__device__ __forceinline__ void sh_dc_eff(const float *dc, int F, Weights w, float &d0, float &d1, float &d2) {
+    d0 = 0.f; d1 = 0.f; d2 = 0.f;
+    for (int f = 0; f < F; ++f) {
+        const float wf = w[f];
+        d0 += dc[3 * f] * wf; d1 += dc[3 * f + 1] * wf; d2 += dc[3 * f + 2] * wf;
+    }
+}
+// ... and its backward: v_dc[f, :] = (w[f] * b0) * v
+__device__ __forceinline__ void sh_dc_fan_out(float *v_dc, int F, const float *w, float b0, float v0, float v1,
+                                              float v2) {
+    for (int f = 0; f < F; ++f) {
+        const float wf = w[f] * b0;
+        v_dc[3 * f] = wf * v0; v_dc[3 * f + 1] = wf * v1; v_dc[3 * f + 2] = wf * v2;
+    }
+}
+
+// (a0, a1, a2) += bands K0 .. K-1 dotted with an LDS row whose first entry is band K0
+template <int K0, int K>
+__device__ __forceinline__ void sh_eval_bands(const float *b, int nb, const float *row, float &a0, float &a1,
+                                              float &a2) {
+#pragma unroll
+    for (int k = K0; k < K; ++k) {
+        if (k < nb) {
+            a0 += b[k] * row[3 * (k - K0)];
+            a1 += b[k] * row[3 * (k - K0) + 1];
+            a2 += b[k] * row[3 * (k - K0) + 2];
+        }
+    }
+}
+// the post step clamp(x + 0.5, min=0) and its backward: the gradient passes where the output `c` is positive
+__device__ __forceinline__ void sh_post(float &a0, float &a1, float &a2) {
+    a0 = fmaxf(a0 + 0.5f, 0.f); a1 = fmaxf(a1 + 0.5f, 0.f); a2 = fmaxf(a2 + 0.5f, 0.f);
+}
+__device__ __forceinline__ void sh_post_gate(const float *c, float &v0, float &v1, float &v2) {
+    v0 = c[0] > 0.f ? v0 : 0.f;
+    v1 = c[1] > 0.f ? v1 : 0.f;
+    v2 = c[2] > 0.f ? v2 : 0.f;
+}
+
+// backward of one row: bands K0 .. K-1 of b[k] * v (zero above the active degree) into an LDS row that starts at K0 ...
+template <int K0, int K>
+__device__ __forceinline__ void sh_fill_row(float *row, const float *b, int nb, float v0, float v1, float v2) {
+#pragma unroll
+    for (int k = K0; k < K; ++k) {
+        const float bk = (k < nb) ? b[k] : 0.f;
+        row[3 * (k - K0)] = bk * v0; row[3 * (k - K0) + 1] = bk * v1; row[3 * (k - K0) + 2] = bk * v2;
+    }
+}
+// ... or summed over views into registers
+template <int K>
+__device__ __forceinline__ void sh_accumulate(float (&acc)[3 * K], const float *b, int nb, float v0, float v1,
+                                              float v2) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const float bk = (k < nb) ? b[k] : 0.f;
+        acc[3 * k] += bk * v0; acc[3 * k + 1] += bk * v1; acc[3 * k + 2] += bk * v2;
+    }
+}
+
+// ---- plain SH ---------------------------------------------------------------------------------------------------------
 // One wave (64 lanes) per span of 64 Gaussians; a block is WAVES waves with private LDS slabs and each wave walks
 // spans in a grid-stride loop with the NEXT span's twelve float4 loads already in flight while it evaluates the
 // current one (one span per wave and no prefetch reached 4.1 TB/s where a plain streaming read on this GPU reaches
@@ -176,16 +272,8 @@ __global__ __launch_bounds__(WAVES * 64) void sh_fwd_kernel(int n, int deg, cons
             const int i = g0 + lane;
             float b[25];
             const int nb = sh_bases(x, y, z, deg, b);
-            const float *row = my + lane * LS;
             float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                if (k < nb) {
-                    a0 += b[k] * row[3 * k];
-                    a1 += b[k] * row[3 * k + 1];
-                    a2 += b[k] * row[3 * k + 2];
-                }
-            }
+            sh_eval_bands<0, K>(b, nb, my + lane * LS, a0, a1, a2);
             colors[3 * i] = a0; colors[3 * i + 1] = a1; colors[3 * i + 2] = a2;
         }
         wave_lds_fence();                              // this span's row reads stay ahead of the next span's writes
@@ -206,53 +294,18 @@ __global__ __launch_bounds__(WAVES * 64) void sh_bwd_kernel(int n, int deg, cons
         const int i = g0 + lane;
         float b[25];
         const int nb = sh_bases(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2], deg, b);
-        const float v0 = v_colors[3 * i], v1 = v_colors[3 * i + 1], v2 = v_colors[3 * i + 2];
-        float *row = my + lane * LS;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const float bk = (k < nb) ? b[k] : 0.f;
-            row[3 * k] = bk * v0; row[3 * k + 1] = bk * v1; row[3 * k + 2] = bk * v2;
-        }
+        sh_fill_row<0, K>(my + lane * LS, b, nb, v_colors[3 * i], v_colors[3 * i + 1], v_colors[3 * i + 2]);
     }
     __syncthreads();
-    float *dst = v_coeffs + (size_t)g0 * KC;
-    const int total = cnt * KC;
-    if constexpr (KC % 4 == 0) {
-        float4 *dst4 = reinterpret_cast<float4 *>(dst);
-        for (int t = lane; t < total / 4; t += 64) {
-            const int e = t * 4, r = e / KC, c = e - r * KC;
-            const float *s = my + r * LS + c;
-            dst4[t] = make_float4(s[0], s[1], s[2], s[3]);
-        }
-    } else {
-        for (int e = lane; e < total; e += 64) {
-            const int r = e / KC, c = e - r * KC;
-            dst[e] = my[r * LS + c];
-        }
-    }
-}
-
-__device__ __forceinline__ void fused_viewdir(int i, const float *__restrict__ means,
-                                              const float *__restrict__ cam_pos,
-                                              const int32_t *__restrict__ object_ids,
-                                              const float *__restrict__ poses, float &dx, float &dy, float &dz) {
-    float m0 = means[3 * i], m1 = means[3 * i + 1], m2 = means[3 * i + 2];
-    if (poses != nullptr && object_ids != nullptr) {  // local -> world (scene_graph.py:414)
-        const float *P = poses + 16 * (size_t)object_ids[i];
-        const float w0 = P[0] * m0 + P[1] * m1 + P[2] * m2 + P[9];
-        const float w1 = P[3] * m0 + P[4] * m1 + P[5] * m2 + P[10];
-        const float w2 = P[6] * m0 + P[7] * m1 + P[8] * m2 + P[11];
-        m0 = w0; m1 = w1; m2 = w2;
-    }
-    dx = m0 - cam_pos[0]; dy = m1 - cam_pos[1]; dz = m2 - cam_pos[2];
+    drain_rows<KC, LS, 0, KC % 4 == 0>(v_coeffs + (size_t)g0 * KC, my, cnt, lane);
 }
 
 // ---- fused SH front end (extension) ------------------------------------------------
 // colour = clamp( SH(deg, means - cam_pos, [dc_eff | rest]) + 0.5, min 0 )  with
-// dc_eff = sum_f features_dc[:, f, :] * idft[object, f]   (Fourier "4D-SH" DC term,
-// sgn_splatfacto_scene_graph.py:239-247; F = 1 and idft = [1] for the background model).
+// dc_eff = sum_f features_dc[:, f, :] * idft[object, f]   (F = 1 and idft = [1] for the background model).
 // Replaces, per call: view-dir subtract + norm + divide, the Fourier sum, torch.cat((dc, rest)) (192 MB at
 // 1 M Gaussians), the SH op, +0.5 and clamp — and the matching backward kernels — by one pass.
+// Here and below KC = (K-1)*3 dwords of features_rest per row, LDS row stride KC | 1 (odd).
 template <int K, int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void sh_fwd_fused_kernel(
     int n, int deg, const float *__restrict__ means, const float *__restrict__ cam_pos,
@@ -272,27 +325,11 @@ __global__ __launch_bounds__(WAVES * 64) void sh_fwd_fused_kernel(
     float vx, vy, vz;
     fused_viewdir(i, means, cam_pos, object_ids, poses, vx, vy, vz);
     const int nb = sh_bases(vx, vy, vz, deg, b);
-    const float *w = idft + (size_t)(object_ids ? object_ids[i] : 0) * F;
-    float d0 = 0.f, d1 = 0.f, d2 = 0.f;
-    for (int f = 0; f < F; ++f) {
-        const float wf = w[f];
-        d0 += dc[((size_t)i * F + f) * 3 + 0] * wf;
-        d1 += dc[((size_t)i * F + f) * 3 + 1] * wf;
-        d2 += dc[((size_t)i * F + f) * 3 + 2] * wf;
-    }
+    float d0, d1, d2;
+    sh_dc_eff(dc + (size_t)i * F * 3, F, idft + (size_t)(object_ids ? object_ids[i] : 0) * F, d0, d1, d2);
     float a0 = b[0] * d0, a1 = b[0] * d1, a2 = b[0] * d2;
-    if constexpr (KC > 0) {
-        const float *row = my + lane * LS;
-#pragma unroll
-        for (int k = 1; k < K; ++k) {
-            if (k < nb) {
-                a0 += b[k] * row[3 * (k - 1)];
-                a1 += b[k] * row[3 * (k - 1) + 1];
-                a2 += b[k] * row[3 * (k - 1) + 2];
-            }
-        }
-    }
-    if (post) { a0 = fmaxf(a0 + 0.5f, 0.f); a1 = fmaxf(a1 + 0.5f, 0.f); a2 = fmaxf(a2 + 0.5f, 0.f); }
+    sh_eval_bands<1, K>(b, nb, my + lane * LS, a0, a1, a2);
+    if (post) sh_post(a0, a1, a2);
     colors[3 * i] = a0; colors[3 * i + 1] = a1; colors[3 * i + 2] = a2;
 }
 
@@ -315,36 +352,13 @@ __global__ __launch_bounds__(WAVES * 64) void sh_bwd_fused_kernel(
         fused_viewdir(i, means, cam_pos, object_ids, poses, vx, vy, vz);
         const int nb = sh_bases(vx, vy, vz, deg, b);
         float v0 = v_colors[3 * i], v1 = v_colors[3 * i + 1], v2 = v_colors[3 * i + 2];
-        if (post) {  // clamp(x + 0.5, min=0): gradient passes where the output is positive
-            v0 = colors[3 * i] > 0.f ? v0 : 0.f;
-            v1 = colors[3 * i + 1] > 0.f ? v1 : 0.f;
-            v2 = colors[3 * i + 2] > 0.f ? v2 : 0.f;
-        }
-        const float *w = idft + (size_t)(object_ids ? object_ids[i] : 0) * F;
-        for (int f = 0; f < F; ++f) {
-            const float wf = w[f] * b[0];
-            v_dc[((size_t)i * F + f) * 3 + 0] = wf * v0;
-            v_dc[((size_t)i * F + f) * 3 + 1] = wf * v1;
-            v_dc[((size_t)i * F + f) * 3 + 2] = wf * v2;
-        }
-        if constexpr (KC > 0) {
-            float *row = my + lane * LS;
-#pragma unroll
-            for (int k = 1; k < K; ++k) {
-                const float bk = (k < nb) ? b[k] : 0.f;
-                row[3 * (k - 1)] = bk * v0; row[3 * (k - 1) + 1] = bk * v1; row[3 * (k - 1) + 2] = bk * v2;
-            }
-        }
+        if (post) sh_post_gate(colors + 3 * i, v0, v1, v2);
+        sh_dc_fan_out(v_dc + (size_t)i * F * 3, F, idft + (size_t)(object_ids ? object_ids[i] : 0) * F, b[0], v0, v1,
+                      v2);
+        sh_fill_row<1, K>(my + lane * LS, b, nb, v0, v1, v2);
     }
     __syncthreads();
-    if constexpr (KC > 0) {
-        float *dst = v_rest + (size_t)g0 * KC;
-        const int total = cnt * KC;
-        for (int e = lane; e < total; e += 64) {
-            const int r = e / KC, c = e - r * KC;
-            dst[e] = my[r * LS + c];
-        }
-    }
+    if constexpr (KC > 0) drain_rows<KC, LS, 0, false>(v_rest + (size_t)g0 * KC, my, cnt, lane);
 }
 
 // ---- fused SH over UN-CONCATENATED sub-models (round 4) ---------------------------------------------------------------
@@ -368,10 +382,23 @@ struct ShParts {
     float *v_rest[SH_MAX_PARTS];
 };
 
-__device__ __forceinline__ int sh_part_of(const ShParts &P, int span) {
-    int p = 0;
-    while (p + 1 < P.n_parts && span >= P.span0[p + 1]) ++p;
-    return p;
+// the part `p` that grid span `span` belongs to, the span's first row INSIDE that part and its row count (0 rows
+// behind the last span)
+__device__ __forceinline__ void sh_part_span(const ShParts &P, int span, int &p, int &r0, int &cnt) {
+    const bool live = span < P.span0[P.n_parts];
+    p = 0;
+    if (live)
+        while (p + 1 < P.n_parts && span >= P.span0[p + 1]) ++p;
+    r0 = live ? (span - P.span0[p]) * 64 : 0;
+    cnt = live ? max(0, min(64, P.rows[p] - r0)) : 0;
+}
+// view direction of aggregated row i, a row of part (= object) p
+__device__ __forceinline__ int sh_part_bases(int i, int p, const float *__restrict__ means,
+                                             const float *__restrict__ cam_pos, const float *__restrict__ poses,
+                                             int deg, float *b) {
+    float m0 = means[3 * i], m1 = means[3 * i + 1], m2 = means[3 * i + 2];
+    if (poses != nullptr) pose_apply(poses + 16 * (size_t)p, m0, m1, m2);
+    return sh_bases(m0 - cam_pos[0], m1 - cam_pos[1], m2 - cam_pos[2], deg, b);
 }
 
 template <int K, int WAVES>
@@ -382,47 +409,21 @@ __global__ __launch_bounds__(WAVES * 64) void sh_fwd_parts_kernel(
     constexpr int KC = (K - 1) * 3, LS = (KC | 1);
     __shared__ float lds[WAVES][64 * (KC > 0 ? LS : 1)];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int span = blockIdx.x * WAVES + wave;
-    const bool live = span < P.span0[P.n_parts];
-    const int p = live ? sh_part_of(P, span) : 0;
-    const int r0 = live ? (span - P.span0[p]) * 64 : 0;           // first row of the span INSIDE its part
-    const int cnt = live ? max(0, min(64, P.rows[p] - r0)) : 0;
+    int p, r0, cnt;
+    sh_part_span(P, blockIdx.x * WAVES + wave, p, r0, cnt);
     float *my = lds[wave];
     if constexpr (KC > 0) stage_rows<KC, LS>(my, P.rest[p] + (size_t)r0 * KC, cnt, lane);
     __syncthreads();
     if (lane >= cnt) return;
     const int r = r0 + lane, i = P.row0[p] + r;
     float b[25];
-    float m0 = means[3 * i], m1 = means[3 * i + 1], m2 = means[3 * i + 2];
-    if (poses != nullptr) {                                      // local -> world (scene_graph.py:414); row p
-        const float *Q = poses + 16 * (size_t)p;
-        const float w0 = Q[0] * m0 + Q[1] * m1 + Q[2] * m2 + Q[9];
-        const float w1 = Q[3] * m0 + Q[4] * m1 + Q[5] * m2 + Q[10];
-        const float w2 = Q[6] * m0 + Q[7] * m1 + Q[8] * m2 + Q[11];
-        m0 = w0; m1 = w1; m2 = w2;
-    }
-    const int nb = sh_bases(m0 - cam_pos[0], m1 - cam_pos[1], m2 - cam_pos[2], deg, b);
+    const int nb = sh_part_bases(i, p, means, cam_pos, poses, deg, b);
     const int F = P.F[p];
-    const float *w = idft + (size_t)p * idft_stride;
-    const float *dc = P.dc[p] + (size_t)r * F * 3;
-    float d0 = 0.f, d1 = 0.f, d2 = 0.f;
-    for (int f = 0; f < F; ++f) {
-        const float wf = w[f];
-        d0 += dc[3 * f] * wf; d1 += dc[3 * f + 1] * wf; d2 += dc[3 * f + 2] * wf;
-    }
+    float d0, d1, d2;
+    sh_dc_eff(P.dc[p] + (size_t)r * F * 3, F, idft + (size_t)p * idft_stride, d0, d1, d2);
     float a0 = b[0] * d0, a1 = b[0] * d1, a2 = b[0] * d2;
-    if constexpr (KC > 0) {
-        const float *row = my + lane * LS;
-#pragma unroll
-        for (int k = 1; k < K; ++k) {
-            if (k < nb) {
-                a0 += b[k] * row[3 * (k - 1)];
-                a1 += b[k] * row[3 * (k - 1) + 1];
-                a2 += b[k] * row[3 * (k - 1) + 2];
-            }
-        }
-    }
-    if (post) { a0 = fmaxf(a0 + 0.5f, 0.f); a1 = fmaxf(a1 + 0.5f, 0.f); a2 = fmaxf(a2 + 0.5f, 0.f); }
+    sh_eval_bands<1, K>(b, nb, my + lane * LS, a0, a1, a2);
+    if (post) sh_post(a0, a1, a2);
     colors[3 * i] = a0; colors[3 * i + 1] = a1; colors[3 * i + 2] = a2;
 }
 
@@ -434,56 +435,22 @@ __global__ __launch_bounds__(WAVES * 64) void sh_bwd_parts_kernel(
     constexpr int KC = (K - 1) * 3, LS = (KC | 1);
     __shared__ float lds[WAVES][64 * (KC > 0 ? LS : 1)];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int span = blockIdx.x * WAVES + wave;
-    const bool live = span < P.span0[P.n_parts];
-    const int p = live ? sh_part_of(P, span) : 0;
-    const int r0 = live ? (span - P.span0[p]) * 64 : 0;
-    const int cnt = live ? max(0, min(64, P.rows[p] - r0)) : 0;
+    int p, r0, cnt;
+    sh_part_span(P, blockIdx.x * WAVES + wave, p, r0, cnt);
     float *my = lds[wave];
     if (lane < cnt) {
         const int r = r0 + lane, i = P.row0[p] + r;
         float b[25];
-        float m0 = means[3 * i], m1 = means[3 * i + 1], m2 = means[3 * i + 2];
-        if (poses != nullptr) {
-            const float *Q = poses + 16 * (size_t)p;
-            const float w0 = Q[0] * m0 + Q[1] * m1 + Q[2] * m2 + Q[9];
-            const float w1 = Q[3] * m0 + Q[4] * m1 + Q[5] * m2 + Q[10];
-            const float w2 = Q[6] * m0 + Q[7] * m1 + Q[8] * m2 + Q[11];
-            m0 = w0; m1 = w1; m2 = w2;
-        }
-        const int nb = sh_bases(m0 - cam_pos[0], m1 - cam_pos[1], m2 - cam_pos[2], deg, b);
+        const int nb = sh_part_bases(i, p, means, cam_pos, poses, deg, b);
         float v0 = v_colors[3 * i], v1 = v_colors[3 * i + 1], v2 = v_colors[3 * i + 2];
-        if (post) {  // clamp(x + 0.5, min=0): gradient passes where the output is positive
-            v0 = colors[3 * i] > 0.f ? v0 : 0.f;
-            v1 = colors[3 * i + 1] > 0.f ? v1 : 0.f;
-            v2 = colors[3 * i + 2] > 0.f ? v2 : 0.f;
-        }
+        if (post) sh_post_gate(colors + 3 * i, v0, v1, v2);
         const int F = P.F[p];
-        const float *w = idft + (size_t)p * idft_stride;
-        float *vd = P.v_dc[p] + (size_t)r * F * 3;
-        for (int f = 0; f < F; ++f) {
-            const float wf = w[f] * b[0];
-            vd[3 * f] = wf * v0; vd[3 * f + 1] = wf * v1; vd[3 * f + 2] = wf * v2;
-        }
-        if constexpr (KC > 0) {
-            float *row = my + lane * LS;
-#pragma unroll
-            for (int k = 1; k < K; ++k) {
-                const float bk = (k < nb) ? b[k] : 0.f;
-                row[3 * (k - 1)] = bk * v0; row[3 * (k - 1) + 1] = bk * v1; row[3 * (k - 1) + 2] = bk * v2;
-            }
-        }
+        sh_dc_fan_out(P.v_dc[p] + (size_t)r * F * 3, F, idft + (size_t)p * idft_stride, b[0], v0, v1, v2);
+        sh_fill_row<1, K>(my + lane * LS, b, nb, v0, v1, v2);
     }
     __syncthreads();
     if constexpr (KC > 0) {
-        if (cnt > 0) {
-            float *dst = P.v_rest[p] + (size_t)r0 * KC;
-            const int total = cnt * KC;
-            for (int e = lane; e < total; e += 64) {
-                const int r = e / KC, c = e - r * KC;
-                dst[e] = my[r * LS + c];
-            }
-        }
+        if (cnt > 0) drain_rows<KC, LS, 0, false>(P.v_rest[p] + (size_t)r0 * KC, my, cnt, lane);
     }
 }
 
@@ -523,77 +490,149 @@ __global__ __launch_bounds__(WAVES * 64) void sh_bwd_multi_kernel(
             float b[25];
             const int nb = sh_bases(dx, dy, dz, deg, b);
             const float *v = v_colors_all + ((size_t)r * n + i) * 3;
-            const float v0 = v[0], v1 = v[1], v2 = v[2];
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                const float bk = (k < nb) ? b[k] : 0.f;
-                acc[3 * k] += bk * v0; acc[3 * k + 1] += bk * v1; acc[3 * k + 2] += bk * v2;
-            }
+            sh_accumulate<K>(acc, b, nb, v[0], v[1], v[2]);
         }
         float *row = my + lane * LS;
 #pragma unroll
         for (int e = 0; e < KC; ++e) row[e] = acc[e] * scale;
     }
     __syncthreads();
-    const int total = cnt * KC;
-    if (v_dc == nullptr) {
-        float *dst = v_coeffs + (size_t)g0 * KC;
-        for (int e = lane; e < total; e += 64) {
-            const int r = e / KC, c = e - r * KC;
-            dst[e] = my[r * LS + c];
-        }
-    } else {                       // the two leaves of the reference (features_dc, features_rest) get their own tensor
-        for (int e = lane; e < cnt * 3; e += 64) v_dc[(size_t)g0 * 3 + e] = my[(e / 3) * LS + (e % 3)];
-        if constexpr (KC > 3) {
-            constexpr int RC = KC - 3;
-            float *dst = v_coeffs + (size_t)g0 * RC;
-            for (int e = lane; e < cnt * RC; e += 64) {
-                const int r = e / RC, c = e - r * RC;
-                dst[e] = my[r * LS + 3 + c];
-            }
-        }
+    if (v_dc == nullptr) drain_rows<KC, LS, 0, false>(v_coeffs + (size_t)g0 * KC, my, cnt, lane);
+    else drain_dc_rest<KC, LS>(v_dc, v_coeffs, g0, my, cnt, lane);
+}
+
+// ---- batched views (include/sgn_rast.h "Batched views") -----------------------------------------------------------------
+// The fused SH front end for B cameras at once: a wave stages its 64 rows of features_rest into LDS ONCE and every lane
+// evaluates its Gaussian from each camera of the table, colour row b * n + i.  Per view the arithmetic is
+// sh_fwd_fused_kernel's with n_fourier = 1 and idft = {1} (dc_eff = 0 + dc * 1), operation by operation.  The backward
+// sums the views' coefficient gradients in registers in ascending view order (as sh_bwd_multi_kernel, plus the
+// clamp's mask of the fused backward) and writes each coefficient once: no atomics.
+template <int K, int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void sh_views_fwd_kernel(int n, int deg, const SgnViews views,
+                                                                  const float *__restrict__ means,
+                                                                  const float *__restrict__ dc,
+                                                                  const float *__restrict__ rest, int post,
+                                                                  float *__restrict__ colors) {
+    constexpr int KC = (K - 1) * 3, LS = (KC | 1);
+    __shared__ float lds[WAVES][64 * (KC > 0 ? LS : 1)];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int g0 = (blockIdx.x * WAVES + wave) * 64;
+    const int cnt = max(0, min(64, n - g0));
+    float *my = lds[wave];
+    if constexpr (KC > 0) stage_rows<KC, LS>(my, rest + (size_t)g0 * KC, cnt, lane);
+    __syncthreads();
+    if (lane >= cnt) return;
+    const int i = g0 + lane;
+    const float m0 = means[3 * i], m1 = means[3 * i + 1], m2 = means[3 * i + 2];
+    float d0, d1, d2;
+    sh_dc_eff(dc + 3 * i, 1, ShUnitWeight{}, d0, d1, d2);
+    for (int v = 0; v < views.n; ++v) {
+        float b[25];
+        const int nb = sh_bases(m0 - views.pos[v][0], m1 - views.pos[v][1], m2 - views.pos[v][2], deg, b);
+        float a0 = b[0] * d0, a1 = b[0] * d1, a2 = b[0] * d2;
+        sh_eval_bands<1, K>(b, nb, my + lane * LS, a0, a1, a2);
+        if (post) sh_post(a0, a1, a2);
+        const size_t o = (size_t)v * n + i;
+        colors[3 * o] = a0; colors[3 * o + 1] = a1; colors[3 * o + 2] = a2;
     }
 }
 
-template <int K>
-int launch_fwd(int n, int deg, const float *dirs, const float *coeffs, float *colors, hipStream_t s) {
-    constexpr int WAVES = (K > 16) ? 2 : 4;  // keep static LDS under 64 KiB
-    sgn_timing_begin(SGN_T_SH_FWD, s);
-    // grid-stride over spans: enough workgroups to fill the LDS-limited residency (160 KB / slab bytes per CU) twice
-    const int full = sgn_cdiv(n, WAVES * 64);
-    const int grid = full < 256 * 6 ? full : 256 * 6;
-    hipLaunchKernelGGL((sh_fwd_kernel<K, WAVES>), dim3(grid), dim3(WAVES * 64), 0, s, n, deg, dirs, coeffs, colors);
-    sgn_timing_end(SGN_T_SH_FWD, s);
-    return 0;
+template <int K, int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void sh_views_bwd_kernel(int n, int deg, const SgnViews views,
+                                                                  const float *__restrict__ means, int post,
+                                                                  const float *__restrict__ colors,
+                                                                  const float *__restrict__ v_colors,
+                                                                  float *__restrict__ v_dc, float *__restrict__ v_rest) {
+    constexpr int KC = K * 3, LS = (KC | 1);
+    __shared__ float lds[WAVES][64 * LS];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int g0 = (blockIdx.x * WAVES + wave) * 64;
+    const int cnt = max(0, min(64, n - g0));
+    float *my = lds[wave];
+    if (lane < cnt) {
+        const int i = g0 + lane;
+        const float m0 = means[3 * i], m1 = means[3 * i + 1], m2 = means[3 * i + 2];
+        float acc[KC];
+#pragma unroll
+        for (int e = 0; e < KC; ++e) acc[e] = 0.f;
+        for (int v = 0; v < views.n; ++v) {
+            const size_t o = (size_t)v * n + i;
+            float v0 = v_colors[3 * o], v1 = v_colors[3 * o + 1], v2 = v_colors[3 * o + 2];
+            if (post) sh_post_gate(colors + 3 * o, v0, v1, v2);
+            float b[25];
+            const int nb = sh_bases(m0 - views.pos[v][0], m1 - views.pos[v][1], m2 - views.pos[v][2], deg, b);
+            sh_accumulate<K>(acc, b, nb, v0, v1, v2);
+        }
+        float *row = my + lane * LS;
+#pragma unroll
+        for (int e = 0; e < KC; ++e) row[e] = acc[e];
+    }
+    __syncthreads();
+    drain_dc_rest<KC, LS>(v_dc, v_rest, g0, my, cnt, lane);
 }
-template <int K>
-int launch_bwd(int n, int deg, const float *dirs, const float *v_colors, float *v_coeffs, hipStream_t s) {
-    constexpr int WAVES = (K > 16) ? 2 : 4;
-    sgn_timing_begin(SGN_T_SH_BWD, s);
-    hipLaunchKernelGGL((sh_bwd_kernel<K, WAVES>), dim3(sgn_cdiv(n, WAVES * 64)), dim3(WAVES * 64), 0, s, n,
-                       deg, dirs, v_colors, v_coeffs);
-    sgn_timing_end(SGN_T_SH_BWD, s);
-    return 0;
+
+// ---- host side: what every SH entry point shares --------------------------------------------------------------------
+// The one rule for (k, degree): degree in 0..4, k a full set of bands, and the bands of `degree` within k.  A zero
+// code, or the code and the text of the first condition that fails.
+struct ShArgFault {
+    int code;
+    const char *what;
+};
+ShArgFault sh_k_degree_fault(int k, int degree) {
+    if (!(degree >= 0 && degree <= 4)) return {-2, "degree >= 0 && degree <= 4"};
+    if (!(k == 1 || k == 4 || k == 9 || k == 16 || k == 25)) return {-3, "k == 1 || k == 4 || k == 9 || k == 16 || k == 25"};
+    if (!((degree + 1) * (degree + 1) <= k)) return {-4, "(degree + 1) * (degree + 1) <= k"};
+    return {0, nullptr};
 }
+// ... as three SGN_ARG_CHECKs on the entry's `k` and `degree`
+#define SH_CHECK_K_DEGREE()                                                             \
+    do {                                                                                \
+        const ShArgFault f_ = sh_k_degree_fault(k, degree);                             \
+        if (f_.code) {                                                                  \
+            sgn_set_error("%s: argument check failed: %s", __func__, f_.what);          \
+            return f_.code;                                                             \
+        }                                                                               \
+    } while (0)
+
+constexpr int sh_waves(int K) { return K > 16 ? 2 : 4; }   // waves per block: keeps static LDS under 64 KiB
+
+// Runtime k (checked) -> compile-time K: calls fn(std::integral_constant<int, K>{}).
+template <class Fn>
+void sh_dispatch(int k, Fn &&fn) {
+    switch (k) {
+        case 1: fn(std::integral_constant<int, 1>{}); break;
+        case 4: fn(std::integral_constant<int, 4>{}); break;
+        case 9: fn(std::integral_constant<int, 9>{}); break;
+        case 16: fn(std::integral_constant<int, 16>{}); break;
+        default: fn(std::integral_constant<int, 25>{}); break;
+    }
+}
+// One launch of KERNEL<K, WAVES> for the entry's checked `k`: a wave per span of 64 rows, WAVES spans per block.
+#define SH_LAUNCH(KERNEL, spans, stream, ...)                                                                  \
+    sh_dispatch(k, [&](auto kc_) {                                                                             \
+        constexpr int K_ = decltype(kc_)::value, W_ = sh_waves(K_);                                            \
+        hipLaunchKernelGGL((KERNEL<K_, W_>), dim3(sgn_cdiv((spans), W_)), dim3(W_ * 64), 0, (stream), __VA_ARGS__); \
+    })
 
 }  // namespace
 
 SGN_EXPORT int sgn_sh_fwd(int n, int k, int degree, const float *viewdirs, const float *coeffs,
                           float *colors, sgn_stream_t stream) {
     SGN_ARG_CHECK(n >= 0, -1);
-    SGN_ARG_CHECK(degree >= 0 && degree <= 4, -2);
-    SGN_ARG_CHECK(k == 1 || k == 4 || k == 9 || k == 16 || k == 25, -3);
-    SGN_ARG_CHECK((degree + 1) * (degree + 1) <= k, -4);
+    SH_CHECK_K_DEGREE();
     if (n == 0) return 0;
     SGN_ARG_CHECK(viewdirs && coeffs && colors, -5);
     hipStream_t s = (hipStream_t)stream;
-    switch (k) {
-        case 1: launch_fwd<1>(n, degree, viewdirs, coeffs, colors, s); break;
-        case 4: launch_fwd<4>(n, degree, viewdirs, coeffs, colors, s); break;
-        case 9: launch_fwd<9>(n, degree, viewdirs, coeffs, colors, s); break;
-        case 16: launch_fwd<16>(n, degree, viewdirs, coeffs, colors, s); break;
-        default: launch_fwd<25>(n, degree, viewdirs, coeffs, colors, s); break;
-    }
+    sgn_timing_begin(SGN_T_SH_FWD, s);
+    sh_dispatch(k, [&](auto kc) {
+        constexpr int K = decltype(kc)::value, WAVES = sh_waves(K);
+        // grid-stride over spans: enough workgroups to fill the LDS-limited residency (160 KB / slab bytes per CU) twice
+        const int full = sgn_cdiv(n, WAVES * 64);
+        const int grid = full < 256 * 6 ? full : 256 * 6;
+        hipLaunchKernelGGL((sh_fwd_kernel<K, WAVES>), dim3(grid), dim3(WAVES * 64), 0, s, n, degree, viewdirs, coeffs,
+                           colors);
+    });
+    sgn_timing_end(SGN_T_SH_FWD, s);
     SGN_LAUNCH_CHECK();
     return 0;
 }
@@ -601,38 +640,15 @@ SGN_EXPORT int sgn_sh_fwd(int n, int k, int degree, const float *viewdirs, const
 SGN_EXPORT int sgn_sh_bwd(int n, int k, int degree, const float *viewdirs, const float *v_colors,
                           float *v_coeffs, sgn_stream_t stream) {
     SGN_ARG_CHECK(n >= 0, -1);
-    SGN_ARG_CHECK(degree >= 0 && degree <= 4, -2);
-    SGN_ARG_CHECK(k == 1 || k == 4 || k == 9 || k == 16 || k == 25, -3);
-    SGN_ARG_CHECK((degree + 1) * (degree + 1) <= k, -4);
+    SH_CHECK_K_DEGREE();
     if (n == 0) return 0;
     SGN_ARG_CHECK(viewdirs && v_colors && v_coeffs, -5);
     hipStream_t s = (hipStream_t)stream;
-    switch (k) {
-        case 1: launch_bwd<1>(n, degree, viewdirs, v_colors, v_coeffs, s); break;
-        case 4: launch_bwd<4>(n, degree, viewdirs, v_colors, v_coeffs, s); break;
-        case 9: launch_bwd<9>(n, degree, viewdirs, v_colors, v_coeffs, s); break;
-        case 16: launch_bwd<16>(n, degree, viewdirs, v_colors, v_coeffs, s); break;
-        default: launch_bwd<25>(n, degree, viewdirs, v_colors, v_coeffs, s); break;
-    }
+    sgn_timing_begin(SGN_T_SH_BWD, s);
+    SH_LAUNCH(sh_bwd_kernel, sgn_cdiv(n, 64), s, n, degree, viewdirs, v_colors, v_coeffs);
+    sgn_timing_end(SGN_T_SH_BWD, s);
     SGN_LAUNCH_CHECK();
     return 0;
-}
-
-template <int K>
-static void launch_fwd_fused(int n, int deg, const float *means, const float *cam_pos, const float *dc, int F,
-                             const float *rest, const int32_t *oid, const float *idft, const float *poses, int post,
-                             float *colors, hipStream_t s) {
-    constexpr int WAVES = (K > 16) ? 2 : 4;
-    hipLaunchKernelGGL((sh_fwd_fused_kernel<K, WAVES>), dim3(sgn_cdiv(n, WAVES * 64)), dim3(WAVES * 64), 0, s, n, deg,
-                       means, cam_pos, dc, F, rest, oid, idft, poses, post, colors);
-}
-template <int K>
-static void launch_bwd_fused(int n, int deg, const float *means, const float *cam_pos, int F, const int32_t *oid,
-                             const float *idft, const float *poses, int post, const float *colors, const float *v_colors, float *v_dc,
-                             float *v_rest, hipStream_t s) {
-    constexpr int WAVES = (K > 16) ? 2 : 4;
-    hipLaunchKernelGGL((sh_bwd_fused_kernel<K, WAVES>), dim3(sgn_cdiv(n, WAVES * 64)), dim3(WAVES * 64), 0, s, n, deg,
-                       means, cam_pos, F, oid, idft, poses, post, colors, v_colors, v_dc, v_rest);
 }
 
 SGN_EXPORT int sgn_sh_fwd_fused(int n, int k, int degree, const float *means, const float *cam_pos3,
@@ -640,21 +656,14 @@ SGN_EXPORT int sgn_sh_fwd_fused(int n, int k, int degree, const float *means, co
                                 const int32_t *object_ids, const float *idft, const float *poses, int post_half_clamp,
                                 float *colors, sgn_stream_t stream) {
     SGN_ARG_CHECK(n >= 0, -1);
-    SGN_ARG_CHECK(degree >= 0 && degree <= 4, -2);
-    SGN_ARG_CHECK(k == 1 || k == 4 || k == 9 || k == 16 || k == 25, -3);
-    SGN_ARG_CHECK((degree + 1) * (degree + 1) <= k, -4);
+    SH_CHECK_K_DEGREE();
     SGN_ARG_CHECK(n_fourier >= 1 && n_fourier <= 16, -5);
     if (n == 0) return 0;
     SGN_ARG_CHECK(means && cam_pos3 && features_dc && idft && colors && (k == 1 || features_rest), -6);
     hipStream_t s = (hipStream_t)stream;
     sgn_timing_begin(SGN_T_SH_FWD, s);
-    switch (k) {
-        case 1: launch_fwd_fused<1>(n, degree, means, cam_pos3, features_dc, n_fourier, features_rest, object_ids, idft, poses, post_half_clamp, colors, s); break;
-        case 4: launch_fwd_fused<4>(n, degree, means, cam_pos3, features_dc, n_fourier, features_rest, object_ids, idft, poses, post_half_clamp, colors, s); break;
-        case 9: launch_fwd_fused<9>(n, degree, means, cam_pos3, features_dc, n_fourier, features_rest, object_ids, idft, poses, post_half_clamp, colors, s); break;
-        case 16: launch_fwd_fused<16>(n, degree, means, cam_pos3, features_dc, n_fourier, features_rest, object_ids, idft, poses, post_half_clamp, colors, s); break;
-        default: launch_fwd_fused<25>(n, degree, means, cam_pos3, features_dc, n_fourier, features_rest, object_ids, idft, poses, post_half_clamp, colors, s); break;
-    }
+    SH_LAUNCH(sh_fwd_fused_kernel, sgn_cdiv(n, 64), s, n, degree, means, cam_pos3, features_dc, n_fourier,
+              features_rest, object_ids, idft, poses, post_half_clamp, colors);
     sgn_timing_end(SGN_T_SH_FWD, s);
     SGN_LAUNCH_CHECK();
     return 0;
@@ -665,33 +674,17 @@ SGN_EXPORT int sgn_sh_bwd_fused(int n, int k, int degree, const float *means, co
                                 const float *colors, const float *v_colors, float *v_features_dc,
                                 float *v_features_rest, sgn_stream_t stream) {
     SGN_ARG_CHECK(n >= 0, -1);
-    SGN_ARG_CHECK(degree >= 0 && degree <= 4, -2);
-    SGN_ARG_CHECK(k == 1 || k == 4 || k == 9 || k == 16 || k == 25, -3);
-    SGN_ARG_CHECK((degree + 1) * (degree + 1) <= k, -4);
+    SH_CHECK_K_DEGREE();
     SGN_ARG_CHECK(n_fourier >= 1 && n_fourier <= 16, -5);
     if (n == 0) return 0;
     SGN_ARG_CHECK(means && cam_pos3 && idft && colors && v_colors && v_features_dc && (k == 1 || v_features_rest), -6);
     hipStream_t s = (hipStream_t)stream;
     sgn_timing_begin(SGN_T_SH_BWD, s);
-    switch (k) {
-        case 1: launch_bwd_fused<1>(n, degree, means, cam_pos3, n_fourier, object_ids, idft, poses, post_half_clamp, colors, v_colors, v_features_dc, v_features_rest, s); break;
-        case 4: launch_bwd_fused<4>(n, degree, means, cam_pos3, n_fourier, object_ids, idft, poses, post_half_clamp, colors, v_colors, v_features_dc, v_features_rest, s); break;
-        case 9: launch_bwd_fused<9>(n, degree, means, cam_pos3, n_fourier, object_ids, idft, poses, post_half_clamp, colors, v_colors, v_features_dc, v_features_rest, s); break;
-        case 16: launch_bwd_fused<16>(n, degree, means, cam_pos3, n_fourier, object_ids, idft, poses, post_half_clamp, colors, v_colors, v_features_dc, v_features_rest, s); break;
-        default: launch_bwd_fused<25>(n, degree, means, cam_pos3, n_fourier, object_ids, idft, poses, post_half_clamp, colors, v_colors, v_features_dc, v_features_rest, s); break;
-    }
+    SH_LAUNCH(sh_bwd_fused_kernel, sgn_cdiv(n, 64), s, n, degree, means, cam_pos3, n_fourier, object_ids, idft,
+              poses, post_half_clamp, colors, v_colors, v_features_dc, v_features_rest);
     sgn_timing_end(SGN_T_SH_BWD, s);
     SGN_LAUNCH_CHECK();
     return 0;
-}
-
-template <int K>
-static void launch_bwd_multi(int n, int deg, int R, const float *dirs_all, const float *means, const float *cam_pos,
-                             const int32_t *oid, const float *poses, const float *v_all, float scale, float *out,
-                             float *out_dc, hipStream_t s) {
-    constexpr int WAVES = (K > 16) ? 2 : 4;
-    hipLaunchKernelGGL((sh_bwd_multi_kernel<K, WAVES>), dim3(sgn_cdiv(n, WAVES * 64)), dim3(WAVES * 64), 0, s, n, deg, R,
-                       dirs_all, means, cam_pos, oid, poses, v_all, scale, out, out_dc);
 }
 
 SGN_EXPORT int sgn_sh_bwd_multi(int n, int k, int degree, int n_views, const float *viewdirs_all, const float *means,
@@ -699,21 +692,14 @@ SGN_EXPORT int sgn_sh_bwd_multi(int n, int k, int degree, int n_views, const flo
                                 const float *v_colors_all, float scale, float *v_coeffs, float *v_dc,
                                 sgn_stream_t stream) {
     SGN_ARG_CHECK(n >= 0 && n_views >= 1, -1);
-    SGN_ARG_CHECK(degree >= 0 && degree <= 4, -2);
-    SGN_ARG_CHECK(k == 1 || k == 4 || k == 9 || k == 16 || k == 25, -3);
-    SGN_ARG_CHECK((degree + 1) * (degree + 1) <= k, -4);
+    SH_CHECK_K_DEGREE();
     if (n == 0) return 0;
     SGN_ARG_CHECK(v_colors_all && (v_coeffs || (v_dc && k == 1)), -5);
     SGN_ARG_CHECK((viewdirs_all != nullptr) != (means != nullptr && cam_pos_all != nullptr), -6);
     hipStream_t s = (hipStream_t)stream;
     sgn_timing_begin(SGN_T_SH_BWD, s);
-    switch (k) {
-        case 1: launch_bwd_multi<1>(n, degree, n_views, viewdirs_all, means, cam_pos_all, object_ids, poses, v_colors_all, scale, v_coeffs, v_dc, s); break;
-        case 4: launch_bwd_multi<4>(n, degree, n_views, viewdirs_all, means, cam_pos_all, object_ids, poses, v_colors_all, scale, v_coeffs, v_dc, s); break;
-        case 9: launch_bwd_multi<9>(n, degree, n_views, viewdirs_all, means, cam_pos_all, object_ids, poses, v_colors_all, scale, v_coeffs, v_dc, s); break;
-        case 16: launch_bwd_multi<16>(n, degree, n_views, viewdirs_all, means, cam_pos_all, object_ids, poses, v_colors_all, scale, v_coeffs, v_dc, s); break;
-        default: launch_bwd_multi<25>(n, degree, n_views, viewdirs_all, means, cam_pos_all, object_ids, poses, v_colors_all, scale, v_coeffs, v_dc, s); break;
-    }
+    SH_LAUNCH(sh_bwd_multi_kernel, sgn_cdiv(n, 64), s, n, degree, n_views, viewdirs_all, means, cam_pos_all,
+              object_ids, poses, v_colors_all, scale, v_coeffs, v_dc);
     sgn_timing_end(SGN_T_SH_BWD, s);
     SGN_LAUNCH_CHECK();
     return 0;
@@ -784,9 +770,9 @@ SGN_EXPORT int sgn_fourier_dc_bwd(int n_parts, const int32_t *row0_host, const i
 
 // ---- fused SH over un-concatenated sub-models: entry points
 namespace {
-static int fill_parts(ShParts &P, int n_parts, const int32_t *rows_host, const int32_t *n_fourier_host,
-                      const float *const *dc_host, const float *const *rest_host, float *const *v_dc_host,
-                      float *const *v_rest_host, int k, bool backward) {
+int fill_parts(ShParts &P, int n_parts, const int32_t *rows_host, const int32_t *n_fourier_host,
+               const float *const *dc_host, const float *const *rest_host, float *const *v_dc_host,
+               float *const *v_rest_host, int k, bool backward) {
     if (n_parts < 1 || n_parts > SH_MAX_PARTS || !rows_host || !n_fourier_host) return -1;
     if (backward ? !v_dc_host : !dc_host) return -1;
     P.n_parts = n_parts;
@@ -810,21 +796,6 @@ static int fill_parts(ShParts &P, int n_parts, const int32_t *rows_host, const i
     for (int p = n_parts + 1; p <= SH_MAX_PARTS; ++p) P.span0[p] = span;
     return span;
 }
-template <int K>
-static void launch_fwd_parts(const ShParts &P, int spans, int deg, const float *means, const float *cam, const float *idft,
-                             int stride, const float *poses, int post, float *colors, hipStream_t s) {
-    constexpr int WAVES = (K > 16) ? 2 : 4;
-    hipLaunchKernelGGL((sh_fwd_parts_kernel<K, WAVES>), dim3(sgn_cdiv(spans, WAVES)), dim3(WAVES * 64), 0, s, P, deg, means,
-                       cam, idft, stride, poses, post, colors);
-}
-template <int K>
-static void launch_bwd_parts(const ShParts &P, int spans, int deg, const float *means, const float *cam, const float *idft,
-                             int stride, const float *poses, int post, const float *colors, const float *v_colors,
-                             hipStream_t s) {
-    constexpr int WAVES = (K > 16) ? 2 : 4;
-    hipLaunchKernelGGL((sh_bwd_parts_kernel<K, WAVES>), dim3(sgn_cdiv(spans, WAVES)), dim3(WAVES * 64), 0, s, P, deg, means,
-                       cam, idft, stride, poses, post, colors, v_colors);
-}
 }  // namespace
 
 SGN_EXPORT int sgn_sh_fwd_parts(int n_parts, const int32_t *rows_host, const int32_t *n_fourier_host,
@@ -832,9 +803,7 @@ SGN_EXPORT int sgn_sh_fwd_parts(int n_parts, const int32_t *rows_host, const int
                                 int degree, const float *means, const float *cam_pos3, const float *idft,
                                 int idft_stride, const float *poses, int post_half_clamp, float *colors,
                                 sgn_stream_t stream) {
-    SGN_ARG_CHECK(degree >= 0 && degree <= 4, -2);
-    SGN_ARG_CHECK(k == 1 || k == 4 || k == 9 || k == 16 || k == 25, -3);
-    SGN_ARG_CHECK((degree + 1) * (degree + 1) <= k, -4);
+    SH_CHECK_K_DEGREE();
     SGN_ARG_CHECK(means && cam_pos3 && idft && colors && idft_stride >= 1 && (k == 1 || features_rest_host), -6);
     ShParts P;
     const int spans = fill_parts(P, n_parts, rows_host, n_fourier_host, features_dc_host, features_rest_host, nullptr, nullptr,
@@ -843,13 +812,8 @@ SGN_EXPORT int sgn_sh_fwd_parts(int n_parts, const int32_t *rows_host, const int
     if (spans == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     sgn_timing_begin(SGN_T_SH_FWD, s);
-    switch (k) {
-        case 1: launch_fwd_parts<1>(P, spans, degree, means, cam_pos3, idft, idft_stride, poses, post_half_clamp, colors, s); break;
-        case 4: launch_fwd_parts<4>(P, spans, degree, means, cam_pos3, idft, idft_stride, poses, post_half_clamp, colors, s); break;
-        case 9: launch_fwd_parts<9>(P, spans, degree, means, cam_pos3, idft, idft_stride, poses, post_half_clamp, colors, s); break;
-        case 16: launch_fwd_parts<16>(P, spans, degree, means, cam_pos3, idft, idft_stride, poses, post_half_clamp, colors, s); break;
-        default: launch_fwd_parts<25>(P, spans, degree, means, cam_pos3, idft, idft_stride, poses, post_half_clamp, colors, s); break;
-    }
+    SH_LAUNCH(sh_fwd_parts_kernel, spans, s, P, degree, means, cam_pos3, idft, idft_stride, poses,
+              post_half_clamp, colors);
     sgn_timing_end(SGN_T_SH_FWD, s);
     SGN_LAUNCH_CHECK();
     return 0;
@@ -860,9 +824,7 @@ SGN_EXPORT int sgn_sh_bwd_parts(int n_parts, const int32_t *rows_host, const int
                                 const float *poses, int post_half_clamp, const float *colors, const float *v_colors,
                                 float *const *v_features_dc_host, float *const *v_features_rest_host,
                                 sgn_stream_t stream) {
-    SGN_ARG_CHECK(degree >= 0 && degree <= 4, -2);
-    SGN_ARG_CHECK(k == 1 || k == 4 || k == 9 || k == 16 || k == 25, -3);
-    SGN_ARG_CHECK((degree + 1) * (degree + 1) <= k, -4);
+    SH_CHECK_K_DEGREE();
     SGN_ARG_CHECK(means && cam_pos3 && idft && colors && v_colors && v_features_dc_host && idft_stride >= 1 &&
                       (k == 1 || v_features_rest_host), -6);
     ShParts P;
@@ -872,129 +834,15 @@ SGN_EXPORT int sgn_sh_bwd_parts(int n_parts, const int32_t *rows_host, const int
     if (spans == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     sgn_timing_begin(SGN_T_SH_BWD, s);
-    switch (k) {
-        case 1: launch_bwd_parts<1>(P, spans, degree, means, cam_pos3, idft, idft_stride, poses, post_half_clamp, colors, v_colors, s); break;
-        case 4: launch_bwd_parts<4>(P, spans, degree, means, cam_pos3, idft, idft_stride, poses, post_half_clamp, colors, v_colors, s); break;
-        case 9: launch_bwd_parts<9>(P, spans, degree, means, cam_pos3, idft, idft_stride, poses, post_half_clamp, colors, v_colors, s); break;
-        case 16: launch_bwd_parts<16>(P, spans, degree, means, cam_pos3, idft, idft_stride, poses, post_half_clamp, colors, v_colors, s); break;
-        default: launch_bwd_parts<25>(P, spans, degree, means, cam_pos3, idft, idft_stride, poses, post_half_clamp, colors, v_colors, s); break;
-    }
+    SH_LAUNCH(sh_bwd_parts_kernel, spans, s, P, degree, means, cam_pos3, idft, idft_stride, poses,
+              post_half_clamp, colors, v_colors);
     sgn_timing_end(SGN_T_SH_BWD, s);
     SGN_LAUNCH_CHECK();
     return 0;
 }
 
-// ---- batched views (include/sgn_rast.h "Batched views") -----------------------------------------------------------------
-// The fused SH front end for B cameras at once: a wave stages its 64 rows of features_rest into LDS ONCE and every lane
-// evaluates its Gaussian from each camera of the table, colour row b * n + i.  Per view the arithmetic is
-// sh_fwd_fused_kernel's with n_fourier = 1 and idft = {1} (dc_eff = 0 + dc * 1), operation by operation.  The backward
-// sums the views' coefficient gradients in registers in ascending view order (as sh_bwd_multi_kernel, plus the
-// clamp's mask of the fused backward) and writes each coefficient once: no atomics.
+// ---- batched views: entry points
 namespace {
-
-template <int K, int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void sh_views_fwd_kernel(int n, int deg, const SgnViews views,
-                                                                  const float *__restrict__ means,
-                                                                  const float *__restrict__ dc,
-                                                                  const float *__restrict__ rest, int post,
-                                                                  float *__restrict__ colors) {
-    constexpr int KC = (K - 1) * 3, LS = (KC | 1);
-    __shared__ float lds[WAVES][64 * (KC > 0 ? LS : 1)];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int g0 = (blockIdx.x * WAVES + wave) * 64;
-    const int cnt = max(0, min(64, n - g0));
-    float *my = lds[wave];
-    if constexpr (KC > 0) stage_rows<KC, LS>(my, rest + (size_t)g0 * KC, cnt, lane);
-    __syncthreads();
-    if (lane >= cnt) return;
-    const int i = g0 + lane;
-    const float m0 = means[3 * i], m1 = means[3 * i + 1], m2 = means[3 * i + 2];
-    const float wf = 1.f;
-    const float d0 = 0.f + dc[3 * i] * wf, d1 = 0.f + dc[3 * i + 1] * wf, d2 = 0.f + dc[3 * i + 2] * wf;
-    for (int v = 0; v < views.n; ++v) {
-        float b[25];
-        const int nb = sh_bases(m0 - views.pos[v][0], m1 - views.pos[v][1], m2 - views.pos[v][2], deg, b);
-        float a0 = b[0] * d0, a1 = b[0] * d1, a2 = b[0] * d2;
-        if constexpr (KC > 0) {
-            const float *row = my + lane * LS;
-#pragma unroll
-            for (int k = 1; k < K; ++k) {
-                if (k < nb) {
-                    a0 += b[k] * row[3 * (k - 1)];
-                    a1 += b[k] * row[3 * (k - 1) + 1];
-                    a2 += b[k] * row[3 * (k - 1) + 2];
-                }
-            }
-        }
-        if (post) { a0 = fmaxf(a0 + 0.5f, 0.f); a1 = fmaxf(a1 + 0.5f, 0.f); a2 = fmaxf(a2 + 0.5f, 0.f); }
-        const size_t o = (size_t)v * n + i;
-        colors[3 * o] = a0; colors[3 * o + 1] = a1; colors[3 * o + 2] = a2;
-    }
-}
-
-template <int K, int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void sh_views_bwd_kernel(int n, int deg, const SgnViews views,
-                                                                  const float *__restrict__ means, int post,
-                                                                  const float *__restrict__ colors,
-                                                                  const float *__restrict__ v_colors,
-                                                                  float *__restrict__ v_dc, float *__restrict__ v_rest) {
-    constexpr int KC = K * 3, LS = (KC | 1);
-    __shared__ float lds[WAVES][64 * LS];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int g0 = (blockIdx.x * WAVES + wave) * 64;
-    const int cnt = max(0, min(64, n - g0));
-    float *my = lds[wave];
-    if (lane < cnt) {
-        const int i = g0 + lane;
-        const float m0 = means[3 * i], m1 = means[3 * i + 1], m2 = means[3 * i + 2];
-        float acc[KC];
-#pragma unroll
-        for (int e = 0; e < KC; ++e) acc[e] = 0.f;
-        for (int v = 0; v < views.n; ++v) {
-            const size_t o = (size_t)v * n + i;
-            float v0 = v_colors[3 * o], v1 = v_colors[3 * o + 1], v2 = v_colors[3 * o + 2];
-            if (post) {  // clamp(x + 0.5, min=0): gradient passes where the output is positive
-                v0 = colors[3 * o] > 0.f ? v0 : 0.f;
-                v1 = colors[3 * o + 1] > 0.f ? v1 : 0.f;
-                v2 = colors[3 * o + 2] > 0.f ? v2 : 0.f;
-            }
-            float b[25];
-            const int nb = sh_bases(m0 - views.pos[v][0], m1 - views.pos[v][1], m2 - views.pos[v][2], deg, b);
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                const float bk = (k < nb) ? b[k] : 0.f;
-                acc[3 * k] += bk * v0; acc[3 * k + 1] += bk * v1; acc[3 * k + 2] += bk * v2;
-            }
-        }
-        float *row = my + lane * LS;
-#pragma unroll
-        for (int e = 0; e < KC; ++e) row[e] = acc[e];
-    }
-    __syncthreads();
-    for (int e = lane; e < cnt * 3; e += 64) v_dc[(size_t)g0 * 3 + e] = my[(e / 3) * LS + (e % 3)];
-    if constexpr (KC > 3) {
-        constexpr int RC = KC - 3;
-        float *dst = v_rest + (size_t)g0 * RC;
-        for (int e = lane; e < cnt * RC; e += 64) {
-            const int r = e / RC, c = e - r * RC;
-            dst[e] = my[r * LS + 3 + c];
-        }
-    }
-}
-
-template <int K>
-void launch_views(bool fwd, int n, int deg, const SgnViews &t, const float *means, const float *dc, const float *rest,
-                  int post, const float *colors, const float *v_colors, float *out_colors, float *v_dc, float *v_rest,
-                  hipStream_t s) {
-    constexpr int WAVES = (K > 16) ? 2 : 4;
-    if (fwd)
-        hipLaunchKernelGGL((sh_views_fwd_kernel<K, WAVES>), dim3(sgn_cdiv(n, WAVES * 64)), dim3(WAVES * 64), 0, s, n,
-                           deg, t, means, dc, rest, post, out_colors);
-    else
-        hipLaunchKernelGGL((sh_views_bwd_kernel<K, WAVES>), dim3(sgn_cdiv(n, WAVES * 64)), dim3(WAVES * 64), 0, s, n,
-                           deg, t, means, post, colors, v_colors, v_dc, v_rest);
-}
-
 int sh_views(const char *fn, bool fwd, int n_views, int n, int k, int degree, const sgn_view_cam *cams,
              const float *means, const float *dc, const float *rest, int post, const float *colors,
              const float *v_colors, float *out_colors, float *v_dc, float *v_rest, hipStream_t s) {
@@ -1006,7 +854,7 @@ int sh_views(const char *fn, bool fwd, int n_views, int n, int k, int degree, co
         sgn_set_error("%s: n %d: need n >= 0 and n_views * n < 2^28", fn, n);
         return -2;
     }
-    if (!(k == 1 || k == 4 || k == 9 || k == 16 || k == 25) || degree < 0 || (degree + 1) * (degree + 1) > k) {
+    if (sh_k_degree_fault(k, degree).code) {
         sgn_set_error("%s: k %d / degree %d", fn, k, degree);
         return -3;
     }
@@ -1018,18 +866,12 @@ int sh_views(const char *fn, bool fwd, int n_views, int n, int k, int degree, co
     if (n == 0) return 0;
     const SgnViews t = sgn_views_table(n_views, cams, 16, 16, false);
     sgn_timing_begin(fwd ? SGN_T_SH_FWD : SGN_T_SH_BWD, s);
-    switch (k) {
-        case 1: launch_views<1>(fwd, n, degree, t, means, dc, rest, post, colors, v_colors, out_colors, v_dc, v_rest, s); break;
-        case 4: launch_views<4>(fwd, n, degree, t, means, dc, rest, post, colors, v_colors, out_colors, v_dc, v_rest, s); break;
-        case 9: launch_views<9>(fwd, n, degree, t, means, dc, rest, post, colors, v_colors, out_colors, v_dc, v_rest, s); break;
-        case 16: launch_views<16>(fwd, n, degree, t, means, dc, rest, post, colors, v_colors, out_colors, v_dc, v_rest, s); break;
-        default: launch_views<25>(fwd, n, degree, t, means, dc, rest, post, colors, v_colors, out_colors, v_dc, v_rest, s); break;
-    }
+    if (fwd) SH_LAUNCH(sh_views_fwd_kernel, sgn_cdiv(n, 64), s, n, degree, t, means, dc, rest, post, out_colors);
+    else SH_LAUNCH(sh_views_bwd_kernel, sgn_cdiv(n, 64), s, n, degree, t, means, post, colors, v_colors, v_dc, v_rest);
     sgn_timing_end(fwd ? SGN_T_SH_FWD : SGN_T_SH_BWD, s);
     SGN_LAUNCH_CHECK();
     return 0;
 }
-
 }  // namespace
 
 SGN_EXPORT int sgn_sh_views_fwd(int n_views, int n, int k, int degree, const sgn_view_cam *cams, const float *means,

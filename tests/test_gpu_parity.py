@@ -152,6 +152,20 @@ def test_sh_forward_backward(hip, c_oracle, k, deg, n):
     assert (cd.grad[:, (deg + 1) ** 2:, :] == 0).all()          # inactive bands: exact zeros
 
 
+@pytest.mark.parametrize("k,deg,n", [(16, 3, 193), (1, 0, 193), (1, 0, 130)])
+def test_sh_forward_of_coefficients_at_an_odd_storage_offset_equals_the_aligned_call(hip, k, deg, n):
+    """A contiguous view 4 bytes into its storage takes the dword stage-in instead of the float4 one: same bits.
+    193 rows: three full spans and a one-row span (k = 1: three floats, all tail, no float4); 130 rows, k = 1: a two-row
+    last span, one float4 and a two-float tail in the aligned call."""
+    g = torch.Generator().manual_seed(n * 31 + k)
+    dirs = (torch.randn(n, 3, generator=g) * 2).to(DEV)
+    store = torch.randn(n * k * 3 + 1, generator=g).to(DEV)
+    odd = store[1:].reshape(n, k, 3)
+    aligned = odd.clone()
+    assert odd.is_contiguous() and odd.data_ptr() % 16 == 4 and aligned.data_ptr() % 16 == 0
+    assert torch.equal(hip.spherical_harmonics(deg, dirs, odd), hip.spherical_harmonics(deg, dirs, aligned))
+
+
 # ------------------------------------------------------------------ binning
 @pytest.mark.parametrize("n", [1, 5, 2047, 2048, 2049, 100_000, 1_000_003])
 def test_scan_bit_exact(hip, n):

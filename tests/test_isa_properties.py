@@ -122,6 +122,10 @@ def test_streaming_kernels_issue_their_loads_before_the_first_lds_write(tmp_path
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not available")
     sh = _kernels(_asm(tmp_path_factory, "sh"))
+    # nine SH kernel templates x five K, plus fourier_dc_bwd_kernel: none dropped, and no shared helper spills
+    assert len(sh) == 46, sorted(sh)
+    for k, t in sh.items():
+        assert re.search(r"ScratchSize: 0\b", t), f"{k} spills to scratch"
     fwd = next(t for k, t in sh.items() if "sh_fwd_kernelILi16ELi4E" in k)
     fast = fwd[fwd.index("global_load_dwordx4"):]                 # the aligned fast path: 12 float4 per lane
     first_store = min(i for i in (fast.find("ds_write"), fast.find("ds_store")) if i >= 0)
