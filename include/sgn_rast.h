@@ -524,6 +524,63 @@ int sgn_raster_layers_fwd(int img_h, int img_w, int block_width, int n, int64_t 
  *   rgb [3][H,W,3], acc [3][H,W], depth [H,W]. */
 int sgn_layers_finish(int img_h, int img_w, const float *layer_img, const float *layer_Ts, const float *depth_channel,
                       const float *sky, float *rgb, float *acc, float *depth, sgn_stream_t stream);
+/* The FEATURE rasterizer (csrc/raster_features.hip; upstream's counterpart is the N-D path of rasterize_gaussians, which
+ * the reference never takes): alpha-composites n_channels (K, 1..64) arbitrary per-Gaussian values features [n,K] over an
+ * existing depth list — class logits, the projection's depths, object ids — evaluating each (pixel, Gaussian) alpha once
+ * per chunk of up to 16 channels (K <= 16: one walk of the lists; K <= 64: ceil(K / 16) walks inside the one call), where
+ * the 3-channel entries need ceil(K / 3) passes.  The per-entry arithmetic is the contract of sgn_raster_fwd (header of
+ * csrc/raster.hip), operation for operation, so every channel of out_img, final_Ts and final_idx are BIT-EQUAL to a
+ * 3-channel pass that carries that channel, in both exact_exp modes (tests/test_gpu_features.py).
+ *   out_img [H,W,K] = F + T * background      final_Ts [H,W]      final_idx [H,W]
+ * List, bins, xys, conics, opacities, opacity_is_logit (0 / 1), opts (exact_exp and ids_qmask are read; NULL = defaults)
+ * and stream mean what they mean to sgn_raster_fwd.  Whole scene only: no id range, no window, no launch order.
+ * background [K] may be NULL (zeros, the natural background of features).  ws >=
+ * sgn_raster_features_workspace_bytes(n) receives the per-Gaussian geometry rows; nothing in it has to survive the call.
+ * n_isect == 0: the list pointers, the per-Gaussian arrays and ws may be NULL; out_img = background, final_Ts = 1,
+ * final_idx = 0.
+ * Errors (checked in this order, before any launch): -12 block_width != 16; -1 image size / n; -13 n_channels outside
+ * 1..64; -3 n_isect; -4 a NULL output; -5 a NULL input (n_isect > 0); -6 ws too small; -11 ids_qmask with n >= 2^28. */
+size_t sgn_raster_features_workspace_bytes(int n);
+int sgn_raster_features_fwd(int img_h, int img_w, int block_width, int n, int n_channels, int64_t n_isect,
+                            const int32_t *gaussian_ids_sorted, const int32_t *tile_bins, const float *xys,
+                            const float *conics, const float *features /*[n,K]*/, const float *opacities /*[n]*/,
+                            int opacity_is_logit, const float *background /*[K] or NULL*/, float *out_img /*[H,W,K]*/,
+                            float *final_Ts /*[H,W]*/, int32_t *final_idx /*[H,W]*/, void *ws, size_t ws_bytes,
+                            const sgn_raster_opts *opts, sgn_stream_t stream);
+/* Its backward: the reverse per-pixel walk from final_idx with the recursion, the operation order (ra = rcp(1 - alpha),
+ * the T recursion, the v_sigma chain) and the alpha_clamp_bwd handling of sgn_raster_bwd, the chunks' geometry gradients
+ * added into the same per-Gaussian sums (v_alpha is linear in the channels).  v_out_img [H,W,K] and v_out_alpha [H,W] may
+ * each be NULL (zeros).  Outputs, every row written (zero where the Gaussian touched nothing): v_xy [n,2], v_conic [n,3]
+ * ([:,1] is the TRUE derivative, as sgn_raster_bwd's: sgn_project_bwd takes it as is), v_features [n,K], v_opacity [n]
+ * (w.r.t. the probability with opacity_is_logit = 0, w.r.t. the logit with 1).  ws as in the forward (the rows are
+ * rebuilt; the per-Gaussian sums live behind them).  reduce_mode and debug_flags of opts are not read: there is one
+ * reduction, the transposed one.  n == 0 returns 0 at once; n_isect == 0 writes zeros.
+ * Errors: the forward's codes, and -4 also for a NULL gradient output / conics / opacities / ws, -5 a NULL list or state
+ * input (n_isect > 0), -7 alpha_clamp_bwd outside (0, 1). */
+int sgn_raster_features_bwd(int img_h, int img_w, int block_width, int n, int n_channels, int64_t n_isect,
+                            const int32_t *gaussian_ids_sorted, const int32_t *tile_bins, const float *xys,
+                            const float *conics, const float *features, const float *opacities, int opacity_is_logit,
+                            const float *background, const float *final_Ts, const int32_t *final_idx,
+                            const float *v_out_img, const float *v_out_alpha, float alpha_clamp_bwd, float *v_xy,
+                            float *v_conic, float *v_features, float *v_opacity, void *ws, size_t ws_bytes,
+                            const sgn_raster_opts *opts, sgn_stream_t stream);
+/* Softmax cross-entropy of a logit image against a uint8 label map (csrc/semantic_loss.hip; the semantic term of the
+ * Street Gaussians paper; torch.nn.functional.cross_entropy(logits.view(-1, K), labels.view(-1).long(), ignore_index)
+ * with reduction = "mean"):  loss_out[0] = mean over COUNTED pixels of logsumexp(logits[p]) - logits[p, labels[p]].
+ * A pixel counts when labels[p] != ignore_index (-1: none), labels[p] < n_classes and — with mask [H,W] bytes, NULL = no
+ * mask — mask[p] != 0.  The sum (fp64) and the count are reduced on the device into ws (>=
+ * sgn_semantic_ce_workspace_bytes(), 16 bytes), loss_out is DEVICE memory: no host read-back.  No counted pixel: loss 0.
+ * The backward takes the forward's ws (the count) and v_loss (DEVICE, one float) and writes v_logits [H,W,K] =
+ * (softmax - onehot) * v_loss / count, zero on every pixel that does not count (so all zeros, no NaN, when none does).
+ * Errors: -1 image size; -2 n_classes outside 1..64; -3 ignore_index outside -1..255; -4 a NULL pointer (mask may be
+ * NULL); -5 ws too small. */
+size_t sgn_semantic_ce_workspace_bytes(void);
+int sgn_semantic_ce_fwd(int img_h, int img_w, int n_classes, const float *logits /*[H,W,K]*/,
+                        const unsigned char *labels /*[H,W]*/, int ignore_index, const unsigned char *mask,
+                        float *loss_out /*device [1]*/, void *ws, size_t ws_bytes, sgn_stream_t stream);
+int sgn_semantic_ce_bwd(int img_h, int img_w, int n_classes, const float *logits, const unsigned char *labels,
+                        int ignore_index, const unsigned char *mask, const float *v_loss /*device [1]*/, const void *ws,
+                        size_t ws_bytes, float *v_logits /*[H,W,K]*/, sgn_stream_t stream);
 /* ONE call per autograd node (round 5; no upstream counterpart: upstream's rasterize_gaussians drives its five `_C`
  * calls from Python).  The whole forward of `rasterize_gaussians` over the full scene: sgn_bin_prepare ->
  * asynchronous read-back of the intersection count -> sgn_raster_build_rows -> SPECULATIVE sgn_bin_intersect (sized by

@@ -9,9 +9,17 @@ sweeps and the initial parameters), the data-parallel helpers
 (``dp``), the ground-truth feed of the training loop (``feed``: the data set as pinned bytes, prefetched a step ahead), the
 coarse-to-fine resolution schedule on those bytes (``pyramid``: one level of a batch's ground truth in one launch),
 the outbound mirror of the feed (``frames``: a frame's eval outputs packed into writer bytes in one launch, carried to
-pinned memory behind the next render), the call-site replay used by bench/smoke/tests (``step``) and the deterministic synthetic scenes
+pinned memory behind the next render), the feature channels composited over the RGB pass's depth list (``features``:
+K per-Gaussian values in one walk per 16 channels with gradients, the differentiable expected depth, the semantic
+cross-entropy), the call-site replay used by bench/smoke/tests (``step``) and the deterministic synthetic scenes
 (``scenes``).  Sub-modules are imported on demand; none of them has a CPU fallback.
 """
+from .features import (  # noqa: F401
+    expected_depth,
+    rasterize_features,
+    semantic_argmax,
+    semantic_cross_entropy,
+)
 from .feed import Batch, ImageFeed  # noqa: F401
 from .frames import FrameSink, Panel, byte_lut, colormap, pack  # noqa: F401
 from .ops import (  # noqa: F401

@@ -106,6 +106,14 @@ SIGNATURES = {
     "sgn_raster_layers_fwd": (_i, [_i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _sz, _i, _vp, _vp, _vp]),
     "sgn_layers_finish": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sgn_raster_features_workspace_bytes": (_sz, [_i]),
+    "sgn_raster_features_fwd": (_i, [_i, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp,
+                                     _sz, _vp, _vp]),
+    "sgn_raster_features_bwd": (_i, [_i, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp,
+                                     _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "sgn_semantic_ce_workspace_bytes": (_sz, []),
+    "sgn_semantic_ce_fwd": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "sgn_semantic_ce_bwd": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
     "sgn_project_fwd_all": (_i, [_i, _vp, _vp, _f, _vp, _vp, _f, _f, _f, _f, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp,
                                  _vp, _i, _f, _vp, _i, _vp, _vp, _vp, _sz, _i, _vp, _i, _vp]),
     "sgn_project_check_wait": (_i, [_vp, _i, _vp, _vp]),
