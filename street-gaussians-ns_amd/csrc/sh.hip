@@ -628,6 +628,7 @@ SGN_EXPORT int sgn_sh_fwd(int n, int k, int degree, const float *viewdirs, const
         constexpr int K = decltype(kc)::value, WAVES = sh_waves(K);
         // grid-stride over spans: enough workgroups to fill the LDS-limited residency (160 KB / slab bytes per CU) twice
         const int full = sgn_cdiv(n, WAVES * 64);
+        // (tests/sh_fp64.py GRID_CAP and test_gpu_sh_fp64.py's grid-stride cases are sized by this cap)
         const int grid = full < 256 * 6 ? full : 256 * 6;
         hipLaunchKernelGGL((sh_fwd_kernel<K, WAVES>), dim3(grid), dim3(WAVES * 64), 0, s, n, degree, viewdirs, coeffs,
                            colors);

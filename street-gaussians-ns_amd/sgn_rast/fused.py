@@ -248,11 +248,11 @@ _sh_exchange = None
 _ONES: dict = {}
 
 
-def _ones_row(F: int, dev) -> torch.Tensor:
-    """[1,F] ones (the idft row of a model without Fourier DC), made once per device instead of a fill per call."""
-    key = (F, str(dev))
+def _ones_rows(rows: int, F: int, dev) -> torch.Tensor:
+    """[rows,F] ones (the idft table of models without Fourier DC), made once per device instead of a fill per call."""
+    key = (rows, F, str(dev))
     if key not in _ONES:
-        _ONES[key] = torch.ones(1, F, dtype=torch.float32, device=dev)
+        _ONES[key] = torch.ones(rows, F, dtype=torch.float32, device=dev)
     return _ONES[key]
 
 
@@ -266,8 +266,16 @@ class _SHFused(Function):
         means_c, cam_c, dc_c = _f32c(means), _f32c(cam_pos).reshape(-1)[:3].contiguous(), _f32c(features_dc)
         rest_c = _f32c(features_rest) if features_rest is not None else None
         oid = None if object_ids is None else object_ids.detach().to(torch.int32).contiguous()
-        idft_c = _f32c(idft).reshape(-1, F) if idft is not None else _ones_row(F, dev)
         pos = _f32c(poses) if (poses is not None and oid is not None) else None
+        if idft is not None:
+            idft_c = _f32c(idft).reshape(-1, F)
+        else:
+            # unit weights.  The kernels read idft row `object_ids[i]`: with ids (for the pose table) the table needs one
+            # row per object — a single row would be read out of bounds by every object but the first — and ids that
+            # select neither a pose nor a weight are not passed on
+            if pos is None:
+                oid = None
+            idft_c = _ones_rows(1 if oid is None else int(pos.shape[0]), F, dev)
         colors = torch.empty(n, 3, dtype=torch.float32, device=dev)
         L.check(L.load().sgn_sh_fwd_fused(n, k, int(degree), L.ptr(means_c), L.ptr(cam_c), L.ptr(dc_c), F,
                                           L.ptr(rest_c), L.ptr(oid), L.ptr(idft_c), L.ptr(pos), int(bool(post)), L.ptr(colors),
