@@ -10,7 +10,8 @@
 // maximize = False):   exp_avg.lerp_(grad, 1 - beta1);  exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2);
 //   denom = exp_avg_sq.sqrt() / sqrt(1 - beta2^t) + eps;  param.addcdiv_(exp_avg, denom, value = -lr / (1 - beta1^t))
 // (bias corrections are computed on the host in double, like torch's Python scalars).  torch is installed in the
-// test container, so this one is pinned against the real thing (tests/test_gpu_optim.py, tests/test_optim_host.py).
+// test container, so this one is pinned against the real thing: over many steps in tests/test_gpu_optim.py, per element
+// against a float64 step of the same class in tests/test_gpu_adam_fp64.py (definition: tests/adam_fp64.py).
 #include "sgn_common.h"
 
 namespace {
@@ -25,8 +26,7 @@ struct AdamTable {
     float *v[ADAM_MAX_TENSORS];
     long long n[ADAM_MAX_TENSORS];
     float step_size[ADAM_MAX_TENSORS];      // lr / (1 - beta1^t)
-    float inv_bc2_sqrt[ADAM_MAX_TENSORS];   // 1 / sqrt(1 - beta2^t)   (torch divides; see kernel)
-    float bc2_sqrt[ADAM_MAX_TENSORS];
+    float bc2_sqrt[ADAM_MAX_TENSORS];       // sqrt(1 - beta2^t)   (torch divides by it; see adam_elem)
     float w1[ADAM_MAX_TENSORS];             // 1 - beta1, rounded from double like torch's Python scalar
     float beta2[ADAM_MAX_TENSORS], w2[ADAM_MAX_TENSORS], eps[ADAM_MAX_TENSORS];
     int blk_start[ADAM_MAX_TENSORS + 1];    // first workgroup of each tensor
@@ -112,7 +112,6 @@ SGN_EXPORT int sgn_adam_step(int count, float *const *params, const float *const
             const double bc2 = 1.0 - pow(beta2[i], (double)steps[i]);
             T.step_size[k] = (float)(lr[i] / bc1);
             T.bc2_sqrt[k] = (float)sqrt(bc2);
-            T.inv_bc2_sqrt[k] = (float)(1.0 / sqrt(bc2));
             // torch hands Python doubles to the elementwise ops, which round them to fp32 once: 1 - 0.999 in double
             // -> 0.001000000047f, not 1.f - 0.999f = 0.00099998713f (a 1.3e-5 relative difference in exp_avg_sq)
             T.w1[k] = (float)(1.0 - beta1[i]); T.beta2[k] = (float)beta2[i]; T.w2[k] = (float)(1.0 - beta2[i]);

@@ -30,6 +30,9 @@ def _launch(rows: List[tuple]) -> None:
     steps = (C.c_int64 * n)(*[int(r[8]) for r in rows])
     L.check(L.load().sgn_adam_step(n, ptrs(0), ptrs(1), ptrs(2), ptrs(3), numel, f32(4), f32(5), f32(6), f32(7), steps,
                                    L.stream_ptr()), "sgn_adam_step")
+    # the kernel wrote through raw pointers: tell autograd, as torch.optim.Adam's in-place ops do.  This package's own
+    # caches (ops._bin_key, ops._window_info, step._world_scene_params) read "same data_ptr, same version" as "same bytes".
+    torch.autograd.graph.increment_version([t for r in rows for t in (r[0], r[2], r[3])])
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -61,7 +64,7 @@ class FusedAdam(torch.optim.Optimizer):
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["step"] += 1
-                rows.append((p.data, p.grad.contiguous(), st["exp_avg"], st["exp_avg_sq"], group["lr"], b1, b2,
+                rows.append((p, p.grad.contiguous(), st["exp_avg"], st["exp_avg_sq"], group["lr"], b1, b2,
                              group["eps"], int(st["step"].item())))
         return rows
 

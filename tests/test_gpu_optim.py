@@ -139,18 +139,20 @@ def _after_train_reference(state, xys_grad, radii, last_size):
                                                       newradii / float(max(last_size[0], last_size[1])))
 
 
-def test_densify_stats_match_after_train():
+@pytest.mark.parametrize("n,size", [(1, (1280, 1920)), (255, (1280, 1920)), (256, (1280, 1920)), (257, (1280, 1920)),
+                                    (5000, (1280, 1920)), (5000, (1920, 1080))],      # (H, W); the last one portrait
+                         ids=lambda v: f"n{v}" if isinstance(v, int) else f"{v[0]}x{v[1]}")
+def test_densify_stats_match_after_train(n, size):
     from sgn_rast import densify
     g = torch.Generator().manual_seed(2)
-    n = 5000
     st_ref = {"xys_grad_norm": None, "vis_counts": None, "max_2Dsize": None}
     st = densify.Stats()
     for it in range(5):
         xys_grad = torch.randn(n, 2, generator=g) * 1e-3
         radii = torch.randint(-1, 40, (n,), generator=g, dtype=torch.int32).clamp(min=0)
         radii[torch.rand(n, generator=g) < 0.3] = 0
-        _after_train_reference(st_ref, xys_grad.clone(), radii.clone(), (1280, 1920))
-        st.update(xys_grad.cuda(), radii.cuda(), (1280, 1920))
+        _after_train_reference(st_ref, xys_grad.clone(), radii.clone(), size)
+        st.update(xys_grad.cuda(), radii.cuda(), size)
     assert torch.equal(st.vis_counts.cpu(), st_ref["vis_counts"])
     assert torch.allclose(st.xys_grad_norm.cpu(), st_ref["xys_grad_norm"], rtol=1e-6, atol=0)
     assert torch.equal(st.max_2Dsize.cpu(), st_ref["max_2Dsize"])
