@@ -1040,6 +1040,63 @@ int sgn_seed_emit(int n, const float *points /*[n,3]*/, int n_boxes, const uint8
                   int32_t *obj_src, int64_t obj_rows, float *bg_world, uint8_t *bg_rgb, int32_t *bg_src, int64_t bg_rows,
                   sgn_stream_t stream);
 
+/* LiDAR DEPTH (the reference supervises depth against images made offline, point by point on the CPU:
+ * data_utils.get_depth_image_from_path loads them).  Sweeps become a per-pixel target on the device, and the pair
+ * features.expected_depth renders — dsum = sum_g depth_g alpha_g T_g and alpha, both [H,W] — becomes a loss with its
+ * gradient and the evaluation depth metrics.  DEVICE: points, depth, out, dsum, alpha, target, mask, loss_out,
+ * count_out / count, v_loss, v_dsum, v_alpha, out5, ws.  HOST: l2w12, cam, the scalars.  Asynchronous on `stream`, no host
+ * read anywhere.  fp32 throughout, no contraction, IEEE division; tests/lidar_depth_oracle.py restates all of it.
+ * TARGET, three calls, so that several sweeps and several LiDARs land in one camera's image:
+ *   sgn_lidar_depth_begin   depth [height,width] = +inf (the bit pattern 0x7f800000).
+ *   sgn_lidar_depth_splat   one sweep: points [n,3] in the LiDAR frame (rows may hold NaN).  pw, live, pc, fu, fv and
+ *       visible are those of "LiDAR SEEDING" above, same parenthesisation, same truncation rule.  A point COUNTS when
+ *       it is live, visible and pc.z <= max_depth; each counted point does one atomic minimum on the uint32 view of
+ *       depth[trunc(fv)][trunc(fu)] with the bits of pc.z (positive floats order as unsigned integers).  The nearest
+ *       return wins whatever the arrival order: bit-identical from run to run, and two sweeps splatted in turn equal
+ *       their concatenation splatted once.
+ *   sgn_lidar_depth_finish  out [height,width], which must not alias depth: 0 where a pixel has no return; a pixel with
+ *       return z keeps it iff  z * (1 - rel_tol) <= m,  m the minimum return over the (2 radius + 1)^2 window clipped
+ *       to the image, the pixel itself included — else 0.  The product is ONE fp32 multiply of z by the fp32 constant
+ *       1.0f - rel_tol, formed on the host.  This is the occlusion filter the LiDAR / camera parallax makes necessary:
+ *       the LiDAR sits above the camera and sees background between foreground returns.  radius 0 keeps every return.
+ * LOSS, one thread per pixel; mask: bytes [H,W], non-zero = keep, NULL = no mask (sgn_rast.loss.check_mask's convention).
+ * With D = dsum / alpha and z = target:
+ *     counted = z > 0  &  alpha > 1e-3  &  dsum > 0  &  (mask == NULL | mask != 0)
+ *     kind 0 (l1):      l = |D - z|            kind 1 (inverse):  l = |1 / D - 1 / z|
+ *     loss = (sum over counted of l) / max(count, 1)
+ * (alpha > 1e-3 is the reference's validity rule for its depth output, sgn_splatfacto.py:995.)  The fp32 per-pixel terms
+ * go into an fp64 sum: per wave with shuffles, across the block's waves through LDS, one fp64 and one integer atomic per
+ * block; a one-thread launch writes loss_out[0] and count_out[0] (int32).  sgn_depth_loss_bwd reads count and v_loss from
+ * device memory; with g = v_loss / max(count, 1), s = sign(D - z) resp. sign(1 / D - 1 / z), 0 at equality:
+ *     l1:       v_dsum = (g s) / alpha                   v_alpha = -v_dsum D
+ *     inverse:  v_dsum = (-(g s) / (D D)) / alpha        v_alpha = -v_dsum D
+ * Uncounted pixels get exact zeros in both; count == 0 gives loss 0 and all-zero gradients, no NaN.
+ * METRICS: sgn_depth_metrics, the same inputs and the same `counted`, one launch; out5 = abs_rel (mean |D - z| / z),
+ * rmse (sqrt(mean (D - z)^2)), mae (mean |D - z|), delta1 (the share with max(D / z, z / D) < 1.25), count (as fp32:
+ * exact up to 2^24 counted pixels); all 0 without a counted pixel.
+ * ws: SGN_DEPTH_LOSS_WS_BYTES of device memory, cleared by the call.  Return codes: -1 n outside
+ * [1, SGN_SEED_MAX_POINTS]; -2 max_depth <= 0, radius outside [0, SGN_LIDAR_DEPTH_MAX_RADIUS], rel_tol outside [0, 1) or
+ * kind outside {0, 1}; -3 width / height outside [1, SGN_SEED_MAX_IMAGE_DIM]; -4 a required pointer is NULL; -5 workspace
+ * too small; -6 out aliases depth.  csrc/lidar_depth.hip. */
+#define SGN_LIDAR_DEPTH_MAX_RADIUS 8
+#define SGN_DEPTH_LOSS_WS_BYTES 64
+#define SGN_DEPTH_LOSS_L1 0
+#define SGN_DEPTH_LOSS_INVERSE 1
+int sgn_lidar_depth_begin(float *depth /*[height,width]*/, int height, int width, sgn_stream_t stream);
+int sgn_lidar_depth_splat(int n, const float *points /*[n,3]*/, const float *l2w12 /*host*/, float min_z, float max_depth,
+                          const sgn_seed_cam *cam /*host*/, float *depth /*[height,width]*/, sgn_stream_t stream);
+int sgn_lidar_depth_finish(const float *depth /*[height,width]*/, int height, int width, int radius, float rel_tol,
+                           float *out /*[height,width]*/, sgn_stream_t stream);
+int sgn_depth_loss_fwd(int img_h, int img_w, const float *dsum, const float *alpha, const float *target,
+                       const unsigned char *mask /*may be NULL*/, int kind, float *loss_out, int32_t *count_out, void *ws,
+                       size_t ws_bytes, sgn_stream_t stream);
+int sgn_depth_loss_bwd(int img_h, int img_w, const float *dsum, const float *alpha, const float *target,
+                       const unsigned char *mask /*may be NULL*/, int kind, const float *v_loss, const int32_t *count,
+                       float *v_dsum, float *v_alpha, sgn_stream_t stream);
+int sgn_depth_metrics(int img_h, int img_w, const float *dsum, const float *alpha, const float *target,
+                      const unsigned char *mask /*may be NULL*/, float *out5, void *ws, size_t ws_bytes,
+                      sgn_stream_t stream);
+
 /* BATCHED VIEWS (no upstream counterpart; gsplat 1.x takes [C] cameras per call).  B = n_views cameras share one image
  * size (img_h, img_w), 16x16 tiles and one set of N Gaussians in the fused front end's raw form (means, log-scales, raw
  * quaternions, opacity logits, features_dc [N,1,3], features_rest [N,k-1,3]; no scene graph).  Row b*N + i of every

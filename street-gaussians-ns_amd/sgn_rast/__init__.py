@@ -11,7 +11,8 @@ coarse-to-fine resolution schedule on those bytes (``pyramid``: one level of a b
 the outbound mirror of the feed (``frames``: a frame's eval outputs packed into writer bytes in one launch, carried to
 pinned memory behind the next render), the feature channels composited over the RGB pass's depth list (``features``:
 K per-Gaussian values in one walk per 16 channels with gradients, the differentiable expected depth, the semantic
-cross-entropy), the call-site replay used by bench/smoke/tests (``step``) and the deterministic synthetic scenes
+cross-entropy), LiDAR depth supervision (``lidar``: sweeps splatted to a per-pixel target, the fused depth loss on the
+expected depth, the evaluation depth metrics), the call-site replay used by bench/smoke/tests (``step``) and the deterministic synthetic scenes
 (``scenes``).  Sub-modules are imported on demand; none of them has a CPU fallback.
 """
 from .features import (  # noqa: F401
@@ -22,6 +23,7 @@ from .features import (  # noqa: F401
 )
 from .feed import Batch, ImageFeed  # noqa: F401
 from .frames import FrameSink, Panel, byte_lut, colormap, pack  # noqa: F401
+from .lidar import depth_loss, depth_metrics, splat_depth  # noqa: F401
 from .ops import (  # noqa: F401
     bin_and_sort_gaussians,
     compute_cumulative_intersects,

@@ -154,6 +154,12 @@ SIGNATURES = {
     "sgn_seed_workspace_bytes": (_sz, [_i, _i]),
     "sgn_seed_classify": (_i, [_i, _vp, _vp, _f, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
     "sgn_seed_emit": (_i, [_i, _vp, _i, _vp, _i, _i, _vp, _sz, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "sgn_lidar_depth_begin": (_i, [_vp, _i, _i, _vp]),
+    "sgn_lidar_depth_splat": (_i, [_i, _vp, _vp, _f, _f, _vp, _vp, _vp]),
+    "sgn_lidar_depth_finish": (_i, [_vp, _i, _i, _i, _f, _vp, _vp]),
+    "sgn_depth_loss_fwd": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "sgn_depth_loss_bwd": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sgn_depth_metrics": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

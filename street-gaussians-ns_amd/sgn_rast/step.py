@@ -504,7 +504,8 @@ def train_step(P: Dict[str, torch.Tensor], cam: Camera, w_img: torch.Tensor, w_a
                sh_degree_to_use: int = 3, block_width: int = 16, with_depth: bool = False, ops=_hip_ops,
                reducer=None, fused: bool = False, sky: Optional[dict] = None, gt: Optional[torch.Tensor] = None,
                ssim_lambda: float = 0.2, loss_fn=None, caller_syncs: bool = False, zero_grad: bool = True,
-               mask: Optional[torch.Tensor] = None, **fused_kw) -> SimpleNamespace:
+               mask: Optional[torch.Tensor] = None, lidar_depth: Optional[torch.Tensor] = None,
+               depth_loss_mult: float = 0.1, depth_loss_kind: str = "l1", **fused_kw) -> SimpleNamespace:
     """One "train-step image": project fwd -> SH fwd -> rasterize(return_alpha) fwd -> scalar loss ->
     full backward to means / log-scales / raw quats / opacity logits / SH coefficients (the metric's definition,
     SURVEY.md §8d: the operator sequence; ``caller_syncs=True`` adds the two host syncs of the reference's own model
@@ -513,13 +514,26 @@ def train_step(P: Dict[str, torch.Tensor], cam: Camera, w_img: torch.Tensor, w_a
     synthetic linear image loss for the reference's photometric loss (``sgn_splatfacto.py:1084-1087``: (1-l) L1 + l
     (1 - SSIM) on ``rgb.clamp(max=1)``), through ``sgn_rast.loss`` or the ``loss_fn(rgb, gt, l)`` the tests pass.
     ``mask`` (bool / uint8 [H,W] or [H,W,1]) is the batch's pixel mask of that loss (``:1081-1083``), see
-    ``sgn_rast.loss.l1_ssim``; a ``loss_fn`` receives it as the keyword ``mask`` only when it is given."""
+    ``sgn_rast.loss.l1_ssim``; a ``loss_fn`` receives it as the keyword ``mask`` only when it is given.
+    ``lidar_depth`` [H,W] float32 (``sgn_rast.lidar.splat_depth``; 0 = no return) adds the LiDAR depth term
+    ``depth_loss_mult * lidar.depth_loss(*features.expected_depth(...), lidar_depth, depth_loss_kind, mask)``: the
+    expected depth is composited over the list the RGB pass binned (nothing is binned again) and ``out.depth_loss`` holds
+    the term's value; an empty view contributes nothing."""
     if mask is not None:           # host-side errors first: before the render, let alone the loss, launches anything
         if gt is None:
             raise ValueError("mask applies to the photometric loss: pass gt as well")
         if loss_fn is None:
             from .loss import check_mask
             check_mask(mask, cam.height, cam.width)
+    if lidar_depth is not None:
+        from . import features, lidar
+        lidar.check_target(lidar_depth, cam.height, cam.width)
+        if depth_loss_kind not in lidar.KINDS:
+            raise ValueError(f"depth_loss_kind must be one of {sorted(lidar.KINDS)}, got {depth_loss_kind!r}")
+        if block_width != 16:
+            raise ValueError("the LiDAR depth term exists for 16x16 tiles only (block_width=16)")
+        if mask is not None:
+            lidar.check_mask(mask, cam.height, cam.width)
     if zero_grad:                  # (False: the caller's loop owns the gradients — keeps and accumulates them, or resets them)
         for p in P.values():
             p.grad = None
@@ -544,7 +558,18 @@ def train_step(P: Dict[str, torch.Tensor], cam: Camera, w_img: torch.Tensor, w_a
         loss = photo + (out.alpha * w_a).sum() / n_pix
     else:
         loss = ((out.rgb * w_img).sum() + (out.alpha * w_a).sum()) / n_pix
-    if loss.requires_grad:         # an empty view (the reference's constant outputs) has nothing to differentiate
+    if lidar_depth is not None:
+        if getattr(out, "empty", False):
+            out.depth_loss = torch.zeros((), device=loss.device)
+        else:
+            # the opacity tensor the RGB pass binned under: its list is reused
+            opac = P["opacity_logits"] if fused else out.opacities
+            dsum, acc = features.expected_depth(out.xys, out.depths, out.radii, out.conics, out.num_tiles_hit, opac,
+                                                cam.height, cam.width, block_width, opacity_is_logit=bool(fused))
+            term = lidar.depth_loss(dsum, acc, lidar_depth, depth_loss_kind, mask)
+            loss = loss + depth_loss_mult * term
+            out.depth_loss = term.detach()
+    if loss.requires_grad:        # an empty view (the reference's constant outputs) has nothing to differentiate
         loss.backward()
     if reducer is not None:
         reducer.finish()
