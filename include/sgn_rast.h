@@ -902,6 +902,25 @@ int sgn_adam_step(int count, float *const *params, const float *const *grads, fl
                   float *const *exp_avg_sqs, const int64_t *numel, const double *lr, const double *beta1,
                   const double *beta2, const double *eps, const int64_t *steps, sgn_stream_t stream);
 
+/* The same step for the rows a view saw (gsplat's SelectiveAdam, the 3DGS trainer's sparse Adam).  sgn_adam_step's
+ * arguments plus three HOST arrays of length `count`: tensor i is rows[i] rows of numel[i] / rows[i] elements;
+ * visible[i] is a DEVICE array of rows[i] entries (NULL allowed for SGN_ADAM_VIS_NONE only) of the type vis_kind[i]
+ * names.  A visible row's param / exp_avg / exp_avg_sq get exactly what sgn_adam_step writes at steps[i], bit for bit;
+ * an invisible row keeps its bits and is neither read nor written (a NaN or an infinity in its gradient or its moments
+ * has no effect).  steps[i] is the caller's global count, as in SelectiveAdam: the bias corrections do not know how
+ * often a row was seen, and the moments of an unseen row do not decay, so this is NOT torch.optim.Adam on a zero
+ * gradient.  Empty tensors are skipped.  Every tensor's arguments are checked before the first launch; return codes:
+ * -1 count < 0; -2 a NULL array; -3 numel[i] < 0 or steps[i] < 1; -4 a NULL tensor pointer with numel[i] > 0;
+ * -5 vis_kind[i] outside 0..2; -6 rows[i] <= 0 with numel[i] > 0; -7 numel[i] % rows[i] != 0; -8 visible[i] NULL with
+ * vis_kind[i] 1 or 2 and numel[i] > 0.  count == 0 returns 0.  Timed in the SGN_T_ADAM slot. */
+#define SGN_ADAM_VIS_NONE 0 /* the tensor steps densely (the sky cube map, for instance) */
+#define SGN_ADAM_VIS_U8 1   /* uint8 / bool, visible if nonzero */
+#define SGN_ADAM_VIS_I32 2  /* int32, visible if > 0: the projection's radii as they are */
+int sgn_adam_step_visible(int count, float *const *params, const float *const *grads, float *const *exp_avgs,
+                          float *const *exp_avg_sqs, const int64_t *numel, const double *lr, const double *beta1,
+                          const double *beta2, const double *eps, const int64_t *steps, const int64_t *rows,
+                          const void *const *visible, const int32_t *vis_kind, sgn_stream_t stream);
+
 /* Per-step densification statistics, SplatfactoModel.after_train (sgn_splatfacto.py:513-541), in one pass and without
  * the host syncs of boolean-mask indexing.  first != 0 initialises the three running buffers (the reference's
  * `is None` branches); max_dim = max(H, W) of the last rendered size. */

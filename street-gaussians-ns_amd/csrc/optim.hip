@@ -79,6 +79,122 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamTable T) {
     }
 }
 
+// --- the visibility-gated step: rows a view did not see keep their bits and cost no parameter traffic ---------------
+// A tensor is `rows` rows of w = n / rows elements; vis has one entry per row.  A float4 whose elements all sit in
+// invisible rows issues no load and no store on p / g / m / v: its lane is masked off for all seven instructions.
+struct AdamVisTable {
+    AdamTable a;
+    long long w[ADAM_MAX_TENSORS];          // elements per row
+    const void *vis[ADAM_MAX_TENSORS];      // one entry per row (kind 1: uint8, kind 2: int32); unused for kind 0
+    unsigned magic[ADAM_MAX_TENSORS];       // floor(2^32 / w) + 1 where 2 <= w < ADAM_CHUNK: x / w = umulhi(x, magic)
+    int kind[ADAM_MAX_TENSORS];             // SGN_ADAM_VIS_*
+};
+static_assert(sizeof(AdamVisTable) <= 4096, "the table travels by value: HIP's kernel-argument limit");
+
+__device__ __forceinline__ bool adam_row_visible(const void *vis, int kind, long long row) {
+    return kind == 2 ? static_cast<const int32_t *>(vis)[row] > 0 : static_cast<const uint8_t *>(vis)[row] != 0;
+}
+
+// Bit k: element k of the float4 that starts at position r of `row` is visible (cnt <= 4 elements exist).  One
+// visibility read per row the float4 touches: one for most float4 of a wide row, up to four at w = 1.
+__device__ __forceinline__ unsigned adam_visible_bits(const void *vis, int kind, long long row, long long r,
+                                                      long long w, int cnt) {
+    bool on = adam_row_visible(vis, kind, row);
+    if (r + cnt <= w) return on ? (1u << cnt) - 1u : 0u;
+    unsigned bits = on ? 1u : 0u;
+#pragma unroll
+    for (int k = 1; k < 4; ++k) {
+        if (k >= cnt) break;
+        if (++r == w) {
+            r = 0;
+            on = adam_row_visible(vis, kind, ++row);
+        }
+        bits |= (on ? 1u : 0u) << k;
+    }
+    return bits;
+}
+
+__global__ __launch_bounds__(256) void adam_visible_kernel(AdamVisTable T) {
+    int t = 0;
+    while (t + 1 < T.a.count && (int)blockIdx.x >= T.a.blk_start[t + 1]) ++t;
+    const long long n = T.a.n[t];
+    const long long base = (long long)(blockIdx.x - T.a.blk_start[t]) * ADAM_CHUNK;
+    float *__restrict__ p = T.a.p[t];
+    const float *__restrict__ g = T.a.g[t];
+    float *__restrict__ m = T.a.m[t];
+    float *__restrict__ v = T.a.v[t];
+    const float w1 = T.a.w1[t], b2 = T.a.beta2[t], w2 = T.a.w2[t];
+    const float bc2 = T.a.bc2_sqrt[t], eps = T.a.eps[t], ss = T.a.step_size[t];
+    const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
+    const void *__restrict__ vis = T.vis[t];
+    const int kind = T.kind[t];
+    const long long w = T.w[t];
+    const unsigned magic = T.magic[t];
+    // row and in-row position of the chunk's first element: the only full division, on wave-uniform operands, once per
+    // workgroup.  An element's own row follows from its offset x < ADAM_CHUNK + w into that row (below).
+    long long row0, rem0;
+    if ((((unsigned long long)base | (unsigned long long)w) >> 32) == 0) {
+        row0 = (unsigned)base / (unsigned)w;
+        rem0 = (unsigned)base % (unsigned)w;
+    } else {
+        row0 = base / w;
+        rem0 = base % w;
+    }
+    // first every visibility read of the thread's four float4 (independent, all in flight together), then the stream
+    unsigned bits[4];
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+        const int l = (it * 256 + (int)threadIdx.x) * 4;
+        const long long i = base + l;
+        bits[it] = 0;
+        if (i >= n) continue;
+        const int cnt = n - i < 4 ? (int)(n - i) : 4;
+        if (kind == 0) {
+            bits[it] = (1u << cnt) - 1u;
+            continue;
+        }
+        long long q, r;
+        if (w == 1) {
+            q = l; r = 0;
+        } else if (w < ADAM_CHUNK) {                 // x < 2 ADAM_CHUNK: the multiply-high quotient is exact
+            const unsigned x = (unsigned)l + (unsigned)rem0;
+            const unsigned qq = __umulhi(x, magic);
+            q = qq; r = x - qq * (unsigned)w;
+        } else {                                     // x < 2 w: the quotient is 0 or 1
+            const long long x = l + rem0;
+            q = x >= w ? 1 : 0; r = x - (q ? w : 0);
+        }
+        bits[it] = adam_visible_bits(vis, kind, row0 + q, r, w, cnt);
+    }
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+        const unsigned b = bits[it];
+        if (b == 0) continue;                        // nothing visible (or past the end): no memory request at all
+        const long long i = base + ((long long)it * 256 + threadIdx.x) * 4;
+        if (vec && i + 4 <= n) {
+            float4 P = *reinterpret_cast<float4 *>(p + i), M = *reinterpret_cast<float4 *>(m + i);
+            float4 V = *reinterpret_cast<float4 *>(v + i);
+            const float4 G = *reinterpret_cast<const float4 *>(g + i);
+            // an invisible element of a partly visible float4 goes back with the bits it was loaded with
+            if (b & 1u) adam_elem(P.x, G.x, M.x, V.x, w1, b2, w2, bc2, eps, ss);
+            if (b & 2u) adam_elem(P.y, G.y, M.y, V.y, w1, b2, w2, bc2, eps, ss);
+            if (b & 4u) adam_elem(P.z, G.z, M.z, V.z, w1, b2, w2, bc2, eps, ss);
+            if (b & 8u) adam_elem(P.w, G.w, M.w, V.w, w1, b2, w2, bc2, eps, ss);
+            *reinterpret_cast<float4 *>(p + i) = P;
+            *reinterpret_cast<float4 *>(m + i) = M;
+            *reinterpret_cast<float4 *>(v + i) = V;
+        } else {
+            for (int k = 0; k < 4; ++k) {            // bits beyond n are never set
+                if (!((b >> k) & 1u)) continue;
+                const long long j = i + k;
+                float P = p[j], M = m[j], V = v[j];
+                adam_elem(P, g[j], M, V, w1, b2, w2, bc2, eps, ss);
+                p[j] = P; m[j] = M; v[j] = V;
+            }
+        }
+    }
+}
+
 }  // namespace
 
 // One Adam step over `count` tensors.  All array arguments are HOST arrays of length `count` (hyper-parameters in
@@ -121,6 +237,62 @@ SGN_EXPORT int sgn_adam_step(int count, float *const *params, const float *const
         }
         T.blk_start[T.count] = blocks;
         if (blocks > 0) hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, s, T);
+    }
+    sgn_timing_end(SGN_T_ADAM, (void *)s);
+    SGN_LAUNCH_CHECK();
+    return 0;
+}
+
+// sgn_adam_step for the rows a view saw (contract: include/sgn_rast.h).  Tensor i is rows[i] rows of numel[i] / rows[i]
+// elements; visible[i] is a DEVICE array of rows[i] entries of the type vis_kind[i] names.  A visible row gets
+// sgn_adam_step's result bit for bit (the same adam_elem, the same host scalars); an invisible row is neither read
+// nor written.  Every row of every tensor is checked before the first launch: an error leaves nothing half stepped.
+SGN_EXPORT int sgn_adam_step_visible(int count, float *const *params, const float *const *grads,
+                                     float *const *exp_avgs, float *const *exp_avg_sqs, const int64_t *numel,
+                                     const double *lr, const double *beta1, const double *beta2, const double *eps,
+                                     const int64_t *steps, const int64_t *rows, const void *const *visible,
+                                     const int32_t *vis_kind, sgn_stream_t stream) {
+    SGN_ARG_CHECK(count >= 0, -1);
+    if (count == 0) return 0;
+    SGN_ARG_CHECK(params && grads && exp_avgs && exp_avg_sqs && numel && lr && beta1 && beta2 && eps && steps, -2);
+    SGN_ARG_CHECK(rows && visible && vis_kind, -2);
+    for (int i = 0; i < count; ++i) {
+        SGN_ARG_CHECK(numel[i] >= 0 && steps[i] >= 1, -3);
+        SGN_ARG_CHECK(vis_kind[i] >= SGN_ADAM_VIS_NONE && vis_kind[i] <= SGN_ADAM_VIS_I32, -5);
+        if (numel[i] == 0) continue;
+        SGN_ARG_CHECK(params[i] && grads[i] && exp_avgs[i] && exp_avg_sqs[i], -4);
+        SGN_ARG_CHECK(rows[i] > 0, -6);
+        SGN_ARG_CHECK(numel[i] % rows[i] == 0, -7);
+        SGN_ARG_CHECK(vis_kind[i] == SGN_ADAM_VIS_NONE || visible[i], -8);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    sgn_timing_begin(SGN_T_ADAM, (void *)s);
+    int i = 0;                                   // consumed ACROSS launches, as in sgn_adam_step: no row steps twice
+    while (i < count) {
+        AdamVisTable T;
+        T.a.count = 0;
+        int blocks = 0;
+        for (; i < count && T.a.count < ADAM_MAX_TENSORS; ++i) {
+            if (numel[i] == 0) continue;
+            const int k = T.a.count++;
+            T.a.p[k] = params[i]; T.a.g[k] = grads[i]; T.a.m[k] = exp_avgs[i]; T.a.v[k] = exp_avg_sqs[i];
+            T.a.n[k] = numel[i];
+            const double bc1 = 1.0 - pow(beta1[i], (double)steps[i]);
+            const double bc2 = 1.0 - pow(beta2[i], (double)steps[i]);
+            T.a.step_size[k] = (float)(lr[i] / bc1);
+            T.a.bc2_sqrt[k] = (float)sqrt(bc2);
+            T.a.w1[k] = (float)(1.0 - beta1[i]); T.a.beta2[k] = (float)beta2[i]; T.a.w2[k] = (float)(1.0 - beta2[i]);
+            T.a.eps[k] = (float)eps[i];
+            const int64_t w = numel[i] / rows[i];
+            T.w[k] = w;
+            T.vis[k] = visible[i];
+            T.kind[k] = vis_kind[i];
+            T.magic[k] = (w >= 2 && w < ADAM_CHUNK) ? (unsigned)((1ull << 32) / (unsigned long long)w) + 1u : 0u;
+            T.a.blk_start[k] = blocks;
+            blocks += (int)sgn_cdiv(numel[i], ADAM_CHUNK);
+        }
+        T.a.blk_start[T.a.count] = blocks;
+        if (blocks > 0) hipLaunchKernelGGL(adam_visible_kernel, dim3(blocks), dim3(256), 0, s, T);
     }
     sgn_timing_end(SGN_T_ADAM, (void *)s);
     SGN_LAUNCH_CHECK();

@@ -64,6 +64,7 @@ SIGNATURES = {
     "sgn_acc_losses_fwd": (_i, [_i64, _vp, _vp, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
     "sgn_acc_losses_bwd": (_i, [_i64, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
     "sgn_adam_step": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sgn_adam_step_visible": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sgn_densify_stats": (_i, [_i, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp]),
     "sgn_densify_workspace_bytes": (_sz, [_i]),
     "sgn_densify_decide": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _vp, _sz, _vp]),
