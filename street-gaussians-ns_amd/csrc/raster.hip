@@ -12,7 +12,9 @@
 //     wave chases gaussian_ids_sorted[k] -> row with scalar loads (s_load_dword, s_load_dwordx8 + x4) into
 //     SGPRs one entry ahead and the VALU instructions take them as scalar operands: no LDS traffic, no VGPRs,
 //     and only the (tile, Gaussian) pairs actually walked are ever fetched.  Lists long enough to leave a
-//     lone wave latency-bound go through 64-entry batches staged in wave-private LDS instead.  (Rounds 1-5 also
+//     lone wave latency-bound go through 64-entry batches staged in wave-private LDS instead.  Both traversals are
+//     written once, in raster_common.h (walk_chase, walk_staged: forward and reverse); the kernels here supply what
+//     they do per entry.  (Rounds 1-5 also
 //     carried a "stream" form — rows copied into depth order first — for A/B runs; it lost everywhere and was
 //     removed in round 6, like the forced one- / four-wave shapes, the XCD swizzle and the MFMA reduction.)
 //   * Per-quadrant wave-uniform skips (`__ballot`) give the early termination and the
@@ -67,26 +69,11 @@ __global__ __launch_bounds__(256) void build_grec_kernel(int n, const float *__r
     const float r = colors[3 * g], gg = colors[3 * g + 1], bl = colors[3 * g + 2];
     float o = opac[g];
     if (opac_is_logit) o = 1.f / (1.f + expf(-o));  // fused torch.sigmoid (sgn_splatfacto.py:949)
-    // bbox of the region where alpha = o*exp(-sigma) can reach 1/255: sigma <= s = ln(255 o) (+1 % margin);
-    // x half-extent sqrt(2 s c / D), y half-extent sqrt(2 s a / D), D = ac - b^2.  Used by the raster kernels
-    // to skip 8x8 quadrants the Gaussian cannot touch (no valid pixel there => results unchanged).
-    const float s = (o * 255.f > 0.f) ? logf(255.f * o) + 0.01f : -1.f;
-    const float D = a * c - b * b;
-    float ex = -1.f, ey = -1.f;
-    if (s >= 0.f) {
-        const bool proper = a > 0.f && c > 0.f && D > 0.f;
-        ex = proper ? sqrtf(2.f * s * c / D) + 1e-3f : 3.0e38f;
-        ey = proper ? sqrtf(2.f * s * a / D) + 1e-3f : 3.0e38f;
-    }
+    float ex, ey;
+    alpha_box(o, a, b, c, ex, ey);
     grec[3 * g + 0] = make_float4(x, y, o, 0.5f * a);
     grec[3 * g + 1] = make_float4(b, 0.5f * c, r, gg);
     grec[3 * g + 2] = make_float4(bl, __int_as_float(g), ex, ey);
-}
-
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
-    return v;
 }
 
 // pixel of (slot q, lane) inside tile (tx,ty).  block 16: four 8x8 quadrants; otherwise linear.
@@ -264,126 +251,63 @@ __device__ __forceinline__ void raster_fwd_tile(int tile, int wv, int W, int H, 
         }
     };
 
+    auto box_mask = [&](int raw, const Rec &cur) __attribute__((always_inline)) -> unsigned {
+        return qm_on ? qm_bits(raw, cur.ex) : quadrant_mask(cur, qcx, qcy, qtest);
+    };
+    // The two ways through the list (raster_common.h): the scalar chase below batch_thresh entries, 64-entry batches
+    // staged in wave-private LDS from there on.
     const int L = range.y - range.x;
-    if (L > 0 && L < batch_thresh) {
-        // short list: chase ids -> rows with scalar loads, one entry ahead (operands arrive in SGPRs)
-        int idc = ids[range.x];                         // raw id word (mask bits included)
-        Rec cur = recs[idc & idmask];
-        float dcur = 0.f;
-        if constexpr (DEPTH) dcur = depths[idc & idmask];
-        int idn = ids[min(range.x + 1, range.y - 1)];
-        for (int k = range.x; k < range.y; ++k) {
-            const Rec nxt = recs[idn & idmask];  // scalar prefetch of the next record
-            float dnxt = 0.f;
-            if constexpr (DEPTH) dnxt = depths[idn & idmask];
-            const int idnn = idn;
-            idn = ids[min(k + 2, range.y - 1)];
-            const unsigned qm = qm_on ? qm_bits(idc, cur.ex) : quadrant_mask(cur, qcx, qcy, qtest);
+    if (L < batch_thresh) {
+        walk_chase<1, DEPTH>(ids, recs, depths, idmask, range.x, range.y - 1, [&](const Rec &cur, int raw, int k, float dep) {
             bool tail; int kg;
-            group_of(idc, k, tail, kg);
-            if (!entry(cur, k, qm, dcur, tail, kg, false)) {
-                if constexpr (GROUPS) rO = (own == (int)tail) ? cO - 1 : cO;   // this entry is still to come
-                break;
-            }
-            cur = nxt;
-            dcur = dnxt;
-            idc = idnn;
-        }
-    } else if (L > 0) {
-        // long list: the one-entry scalar look-ahead leaves a lone wave latency-bound (a dependent id -> row
-        // load pair per entry), so stage 64-entry batches through wave-private LDS instead: lane l gathers
-        // row ids[k0+l] with vector loads a whole batch ahead, entries are then read back with broadcast
-        // ds_read_b128 (no barrier: the workgroup is this one wave and its LDS ops retire in order).
-        const int nb = (L + 63) >> 6;
-        float rd = 0.f;      // DEPTH: the depth of this lane's row of the batch in flight
-        int rid = 0;         // raw id word of this lane's row (quadrant bits on top)
-        auto fetch = [&](int bidx, float4 &r0, float4 &r1, float4 &r2) __attribute__((always_inline)) {
-            const int k = range.x + (bidx << 6) + lane;
-            if (k < range.y) {
-                rid = ids[k];
-                const int id = rid & idmask;
-                const float4 *p = reinterpret_cast<const float4 *>(recs + id);
-                r0 = p[0]; r1 = p[1]; r2 = p[2];
-                if constexpr (DEPTH) rd = depths[id];
-            }
-        };
-        auto row_mask = [&](const float4 &r0, const float4 &r2) __attribute__((always_inline)) -> unsigned {
-            return qm_on ? qm_bits(rid, r2.z) : row_quadrants(r0.x, r0.y, r2.z, r2.w, tx * 16, ty * 16, qtest);
-        };
+            group_of(raw, k, tail, kg);
+            if (entry(cur, k, box_mask(raw, cur), dep, tail, kg, false)) return true;
+            if constexpr (GROUPS) rO = (own == (int)tail) ? cO - 1 : cO;   // this entry is still to come
+            return false;
+        });
+    } else {
         // this wave's quadrants as a bit mask (all four, or the single one of a split tile)
         unsigned mine_q = 0u;
 #pragma unroll
-        for (int q = 0; q < QPW; ++q)
-            if (q >= qlo && q < qhi) mine_q |= 1u << (q0 + q);
-        float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0;
-        fetch(0, r0, r1, r2);
-        stage[0][lane * 3 + 0] = r0; stage[0][lane * 3 + 1] = r1; stage[0][lane * 3 + 2] = r2;
-        if constexpr (DEPTH) stage_d[0][lane] = rd;
-        unsigned qrow = row_mask(r0, r2) & mine_q;
-        bool trow = GROUPS && (rid & idmask) >= split;    // GROUPS: this lane's row belongs to the tail group
-        bool go = true;
-        for (int bi = 0; bi < nb && go; ++bi) {
-            const int cnt = min(64, L - (bi << 6));
-            unsigned long long todo = __ballot(lane < cnt && qrow != 0u);  // entries that can touch my pixels
-            const unsigned long long tmask = GROUPS ? __ballot(lane < cnt && trow) : 0ull;   // the batch's tail entries
-            const unsigned long long omask =       // ... and the entries of the group that has its own list
-                !GROUPS || own < 0 ? 0ull : (own == 1 ? tmask : (__ballot(lane < cnt) & ~tmask));
-            const unsigned qcur = qrow;
-            if (bi + 1 < nb) fetch(bi + 1, r0, r1, r2);   // next batch: in flight while this one is composited
-            const float4 *sb = stage[bi & 1];
-            while (todo) {
-                const int j = __ffsll((long long)todo) - 1;
-                todo &= todo - 1;
-                Rec cur;
-                const float4 a0 = sb[j * 3 + 0], a1 = sb[j * 3 + 1], a2 = sb[j * 3 + 2];
-                cur.x = a0.x; cur.y = a0.y; cur.opac = a0.z; cur.ha = a0.w;
-                cur.b = a1.x; cur.hc = a1.y; cur.r = a1.z; cur.g = a1.w;
-                cur.bl = a2.x; cur.gid = __float_as_int(a2.y); cur.ex = a2.z; cur.ey = a2.w;
-                const unsigned qm = (unsigned)__builtin_amdgcn_readlane((int)qcur, j);
-                float dep = 0.f;
-                if constexpr (DEPTH) dep = stage_d[bi & 1][j];
-                const int k = range.x + (bi << 6) + j;
+        for (int q = 0; q < QPW; ++q) mine_q |= 1u << (q0 + q);
+        // GROUPS: the batch's tail entries, its entries of the group that has its own list, and that group's entries
+        // before the batch
+        unsigned long long tmask = 0ull, omask = 0ull;
+        int cB = 0;
+        walk_staged<1, DEPTH>(
+            ids, recs, depths, idmask, range.x, L, stage, stage_d,
+            [&](int raw, const float4 &r0, const float4 &r2) {
+                return (qm_on ? qm_bits(raw, r2.z) : row_quadrants(r0.x, r0.y, r2.z, r2.w, tx * 16, ty * 16, qtest)) & mine_q;
+            },
+            [&](bool in_batch, int raw) {
+                if constexpr (GROUPS) {
+                    tmask = __ballot(in_batch && (raw & idmask) >= split);
+                    omask = own < 0 ? 0ull : (own == 1 ? tmask : (__ballot(in_batch) & ~tmask));
+                    cB = cO;
+                    cO += __popcll(omask);
+                }
+            },
+            [&](const Rec &cur, int j, int k, unsigned qm, float dep) {
                 bool tail = false; int kg = k;
                 if constexpr (GROUPS) {     // entries of the batch before j that belong to the own-list group
                     tail = (tmask >> j) & 1ull;
-                    if ((omask >> j) & 1ull) kg = baseO + cO + __popcll(omask & ((1ull << j) - 1ull));
+                    if ((omask >> j) & 1ull) kg = baseO + cB + __popcll(omask & ((1ull << j) - 1ull));
                 }
-                if (!entry(cur, k, qm, dep, tail, kg, false)) {
-                    if constexpr (GROUPS) rO = cO + __popcll(omask & ((1ull << j) - 1ull));
-                    go = false;
-                    break;
-                }
-            }
-            if constexpr (GROUPS) cO += __popcll(omask);
-            if (go && bi + 1 < nb) {                      // first use of the prefetched registers
-                float4 *sn = stage[(bi + 1) & 1];
-                sn[lane * 3 + 0] = r0; sn[lane * 3 + 1] = r1; sn[lane * 3 + 2] = r2;
-                if constexpr (DEPTH) stage_d[(bi + 1) & 1][lane] = rd;
-                qrow = row_mask(r0, r2) & mine_q;
-                trow = GROUPS && (rid & idmask) >= split;
-            }
-        }
+                if (entry(cur, k, qm, dep, tail, kg, false)) return true;
+                if constexpr (GROUPS) rO = cB + __popcll(omask & ((1ull << j) - 1ull));
+                return false;
+            });
     }
     if constexpr (GROUPS) {
-        // a group with its own list that outlived the shared walk: the rest of ITS list (scalar chase, one entry ahead)
-        auto own_rest = [&](bool tail, const int2 *gbins, const int32_t *gids, int from) __attribute__((always_inline)) {
-            const int end = gbins[tile].y;
-            if (from >= end) return;
-            int idc = gids[from];
-            Rec cur = recs[idc & idmask];
-            int idn = gids[min(from + 1, end - 1)];
-            for (int p = from; p < end; ++p) {
-                const Rec nxt = recs[idn & idmask];
-                const int idnn = idn;
-                idn = gids[min(p + 2, end - 1)];
-                const unsigned qm = qm_on ? qm_bits(idc, cur.ex) : quadrant_mask(cur, qcx, qcy, qtest);
-                if (!entry(cur, 0, qm, 0.f, tail, p, true)) break;
-                cur = nxt;
-                idc = idnn;
-            }
-        };
         if (rO < 0) rO = cO;
-        if (own >= 0) own_rest(own == 1, Gp->own_bins, Gp->own_ids, baseO + rO);
+        if (own >= 0) {
+            // a group with its own list that outlived the shared walk: the rest of ITS list
+            const int from = baseO + rO;
+            walk_chase<1, false>(Gp->own_ids, recs, nullptr, idmask, from, Gp->own_bins[tile].y - 1,
+                                 [&](const Rec &cur, int raw, int p, float) {
+                                     return entry(cur, 0, box_mask(raw, cur), 0.f, own == 1, p, true);
+                                 });
+        }
         const int HW = W * H, n_tiles2 = 2 * tiles_x * ((H + B - 1) / B);
         float *gT = Gp->state;
         int32_t *gI = reinterpret_cast<int32_t *>(Gp->state + 2 * (size_t)HW);
@@ -596,38 +520,42 @@ __device__ __forceinline__ void raster_fwd_pk_body(int tile, int wv, bool is_lon
         return true;
     };
 
-    if (L > 0 && L < batch_thresh) {
-        int idc = ids[range.x];                         // raw id word (quadrant bits on top)
-        Rec cur = recs[idc & idmask];
-        float dcur = 0.f;
-        if constexpr (DEPTH) dcur = depths[idc & idmask];
-        int idn = ids[min(range.x + 1, range.y - 1)];
-        for (int k = range.x; k < range.y; ++k) {
-            const Rec nxt = recs[idn & idmask];
-            float dnxt = 0.f;
-            if constexpr (DEPTH) dnxt = depths[idn & idmask];
-            const int idnn = idn;
-            idn = ids[min(k + 2, range.y - 1)];
-            const unsigned m = ((qm_on ? qm_bits(idc, cur.ex) : quadrant_mask(cur, qcx, qcy, true)) >> shift_q) & 3u;
+    // which of this wave's two quadrants an entry can touch
+    auto box_mask = [&](int raw, const Rec &cur) __attribute__((always_inline)) -> unsigned {
+        return ((qm_on ? qm_bits(raw, cur.ex) : quadrant_mask(cur, qcx, qcy, true)) >> shift_q) & 3u;
+    };
+    // ... and a staged row (this lane's of a batch)
+    auto row_mask = [&](int raw, const float4 &r0, const float4 &r2) __attribute__((always_inline)) -> unsigned {
+        return ((qm_on ? qm_bits(raw, r2.z) : row_quadrants(r0.x, r0.y, r2.z, r2.w, tx * 16, ty * 16, true)) >> shift_q) & 3u;
+    };
+    if (L < batch_thresh) {
+        walk_chase<1, DEPTH>(ids, recs, depths, idmask, range.x, range.y - 1, [&](const Rec &cur, int raw, int k, float dep) {
+            const unsigned m = box_mask(raw, cur);
             bool tail = false; int kg = k;
             if constexpr (GROUPS) {
-                tail = (idc & idmask) >= G.split;
+                tail = (raw & idmask) >= G.split;
                 if (own == (int)tail) { kg = baseO + cO; ++cO; }
             }
-            if (m != 0u && !entry(cur, k, m, dcur, tail, kg, false)) {
-                if constexpr (GROUPS) rO = (own == (int)tail) ? cO - 1 : cO;   // this entry is still to come
-                break;
-            }
-            cur = nxt;
-            dcur = dnxt;
-            idc = idnn;
-        }
-    } else if (L > 0) {
+            if (m == 0u || entry(cur, k, m, dep, tail, kg, false)) return true;
+            if constexpr (GROUPS) rO = (own == (int)tail) ? cO - 1 : cO;   // this entry is still to come
+            return false;
+        });
+    } else if constexpr (!GROUPS) {
+        walk_staged<1, DEPTH>(
+            ids, recs, depths, idmask, range.x, L, stage, stage_d, row_mask, [](bool, int) {},
+            [&](const Rec &cur, int, int k, unsigned m, float dep) { return entry(cur, k, m, dep, false, k, false); });
+    } else {
+        // The ONE staged walk that is not walk_staged: behind the walker's function boundary this instantiation needs
+        // 8-9 more VGPRs (69 -> 77, 77 -> 84) and loses a wave of occupancy (7 -> 6, 6 -> 5), even with this very
+        // loop text as the walker's body; holding the kernel at its occupancy by attribute spills 28 bytes instead
+        // (profiles/raster_walk.md).  Same discipline as walk_staged (raster_common.h), plus per batch the masks of
+        // the tail entries and of the entries of the group that has its own list.
         const int nb = (L + 63) >> 6;
+        float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0;
         float rd = 0.f;
         int rid = 0;
-        auto fetch = [&](int bidx, float4 &r0, float4 &r1, float4 &r2) __attribute__((always_inline)) {
-            const int k = range.x + (bidx << 6) + lane;
+        auto fetch = [&](int bi) __attribute__((always_inline)) {
+            const int k = range.x + (bi << 6) + lane;
             if (k < range.y) {
                 rid = ids[k];
                 const int id = rid & idmask;
@@ -636,78 +564,53 @@ __device__ __forceinline__ void raster_fwd_pk_body(int tile, int wv, bool is_lon
                 if constexpr (DEPTH) rd = depths[id];
             }
         };
-        auto row_mask = [&](const float4 &r0, const float4 &r2) __attribute__((always_inline)) -> unsigned {
-            return qm_on ? qm_bits(rid, r2.z) : row_quadrants(r0.x, r0.y, r2.z, r2.w, tx * 16, ty * 16, true);
+        auto put = [&](int bi, unsigned &qrow, bool &trow) __attribute__((always_inline)) {
+            float4 *sn = stage[bi & 1];
+            sn[lane * 3 + 0] = r0; sn[lane * 3 + 1] = r1; sn[lane * 3 + 2] = r2;
+            if constexpr (DEPTH) stage_d[bi & 1][lane] = rd;
+            qrow = row_mask(rid, r0, r2);
+            trow = (rid & idmask) >= G.split;       // this lane's row belongs to the tail group
         };
-        float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0;
-        fetch(0, r0, r1, r2);
-        stage[0][lane * 3 + 0] = r0; stage[0][lane * 3 + 1] = r1; stage[0][lane * 3 + 2] = r2;
-        if constexpr (DEPTH) stage_d[0][lane] = rd;
-        unsigned qrow = (row_mask(r0, r2) >> shift_q) & 3u;
-        bool trow = GROUPS && (rid & idmask) >= G.split;      // GROUPS: this lane's row belongs to the tail group
-        bool go = true;
+        unsigned qrow;
+        bool trow, go = true;
+        fetch(0);
+        put(0, qrow, trow);
         for (int bi = 0; bi < nb && go; ++bi) {
             const int cnt = min(64, L - (bi << 6));
             unsigned long long todo = __ballot(lane < cnt && qrow != 0u);
-            const unsigned long long tmask = GROUPS ? __ballot(lane < cnt && trow) : 0ull;
-            const unsigned long long omask =       // the batch's entries of the group that has its own list
-                !GROUPS || own < 0 ? 0ull : (own == 1 ? tmask : (__ballot(lane < cnt) & ~tmask));
+            const unsigned long long tmask = __ballot(lane < cnt && trow);
+            const unsigned long long omask = own < 0 ? 0ull : (own == 1 ? tmask : (__ballot(lane < cnt) & ~tmask));
             const unsigned qcur = qrow;
-            if (bi + 1 < nb) fetch(bi + 1, r0, r1, r2);
-            const float4 *sb = stage[bi & 1];
+            if (bi + 1 < nb) fetch(bi + 1);
             while (todo) {
                 const int j = __ffsll((long long)todo) - 1;
                 todo &= todo - 1;
-                Rec cur;
-                const float4 a0 = sb[j * 3 + 0], a1 = sb[j * 3 + 1], a2 = sb[j * 3 + 2];
-                cur.x = a0.x; cur.y = a0.y; cur.opac = a0.z; cur.ha = a0.w;
-                cur.b = a1.x; cur.hc = a1.y; cur.r = a1.z; cur.g = a1.w;
-                cur.bl = a2.x; cur.gid = __float_as_int(a2.y); cur.ex = a2.z; cur.ey = a2.w;
+                const Rec cur = staged_rec(stage[bi & 1], j);
                 const unsigned m = (unsigned)__builtin_amdgcn_readlane((int)qcur, j);
                 float dep = 0.f;
                 if constexpr (DEPTH) dep = stage_d[bi & 1][j];
-                const int k = range.x + (bi << 6) + j;
-                bool tail = false; int kg = k;
-                if constexpr (GROUPS) {
-                    tail = (tmask >> j) & 1ull;
-                    if ((omask >> j) & 1ull) kg = baseO + cO + __popcll(omask & ((1ull << j) - 1ull));
-                }
-                if (!entry(cur, k, m, dep, tail, kg, false)) {
-                    if constexpr (GROUPS) rO = cO + __popcll(omask & ((1ull << j) - 1ull));
+                const int k = range.x + (bi << 6) + j, before = cO + __popcll(omask & ((1ull << j) - 1ull));
+                if (!entry(cur, k, m, dep, (tmask >> j) & 1ull, ((omask >> j) & 1ull) ? baseO + before : k, false)) {
+                    rO = before;
                     go = false;
                     break;
                 }
             }
-            if constexpr (GROUPS) cO += __popcll(omask);
-            if (go && bi + 1 < nb) {
-                float4 *sn = stage[(bi + 1) & 1];
-                sn[lane * 3 + 0] = r0; sn[lane * 3 + 1] = r1; sn[lane * 3 + 2] = r2;
-                if constexpr (DEPTH) stage_d[(bi + 1) & 1][lane] = rd;
-                qrow = (row_mask(r0, r2) >> shift_q) & 3u;
-                trow = GROUPS && (rid & idmask) >= G.split;
-            }
+            cO += __popcll(omask);
+            if (go && bi + 1 < nb) put(bi + 1, qrow, trow);
         }
     }
     if constexpr (GROUPS) {
-        // a group with its own list that outlived the shared walk: the rest of ITS list (scalar chase, one entry ahead)
-        auto own_rest = [&](bool tail, const int2 *gbins, const int32_t *gids, int from) __attribute__((always_inline)) {
-            const int end = gbins[tile].y;
-            if (from >= end) return;
-            int idc = gids[from];
-            Rec cur = recs[idc & idmask];
-            int idn = gids[min(from + 1, end - 1)];
-            for (int p = from; p < end; ++p) {
-                const Rec nxt = recs[idn & idmask];
-                const int idnn = idn;
-                idn = gids[min(p + 2, end - 1)];
-                const unsigned m = ((qm_on ? qm_bits(idc, cur.ex) : quadrant_mask(cur, qcx, qcy, true)) >> shift_q) & 3u;
-                if (m != 0u && !entry(cur, 0, m, 0.f, tail, p, true)) break;
-                cur = nxt;
-                idc = idnn;
-            }
-        };
         if (rO < 0) rO = cO;
-        if (own >= 0) own_rest(own == 1, G.own_bins, G.own_ids, baseO + rO);
+        if (own >= 0) {
+            // a group with its own list that outlived the shared walk: the rest of ITS list
+            const int from = baseO + rO;
+            walk_chase<1, false>(G.own_ids, recs, nullptr, idmask, from, G.own_bins[tile].y - 1,
+                                 [&](const Rec &cur, int raw, int p, float) {
+                                     const unsigned m = box_mask(raw, cur);
+                                     return m == 0u || entry(cur, 0, m, 0.f, own == 1, p, true);
+                                 });
+        }
         int lh = wave_max_i(max(in0 ? lastH0 : 0, in1 ? lastH1 : 0));
         int lt = wave_max_i(max(in0 ? lastT0 : 0, in1 ? lastT1 : 0));
         if (lane == 0 && lh > 0) atomicMax(G.kmax + 2 * tile, lh);
@@ -767,26 +670,9 @@ __global__ __launch_bounds__(64) void raster_fwd_pk_kernel(int W, int H, int til
     if (skip_flag != nullptr && *skip_flag == 0) return;   // the caller already holds this pass's result (sgn_depth_reuse)
     __shared__ float4 stage[2][64 * 3];
     __shared__ float stage_d[DEPTH ? 2 : 1][64];
-    // The first n_long tiles of the launch order (sgn_tile_order with long_thresh: the longest lists) get four waves
-    // each, the others two.  Blocks come in groups of eight tiles (8 x 4, then 8 x 2 blocks): block b runs on XCD
-    // b % 8, so a tile's waves share an XCD (and its L2) and are dispatched together, longest tiles first.  No block
-    // inside the two regions is empty: interleaving waves that exit at once with working ones left half of the SIMDs
-    // idle (the dispatcher places consecutive workgroups round-robin), 267 vs 159 us on the benchmark scene.
-    const int n_long = tile_order ? min(max(tile_order[n_tiles_], 0), n_tiles_) : 0;
-    const int b_long = ((n_long + 7) >> 3) << 5;
-    const int b = (int)blockIdx.x;
     int t_idx, wv;
-    const bool is_long = b < b_long;
-    if (is_long) {
-        t_idx = (b >> 5) * 8 + (b & 7);
-        wv = (b >> 3) & 3;
-        if (t_idx >= n_long) return;
-    } else {
-        const int b2 = b - b_long;
-        t_idx = n_long + (b2 >> 4) * 8 + (b2 & 7);
-        wv = (b2 >> 3) & 1;
-        if (t_idx >= n_tiles_) return;
-    }
+    bool is_long;
+    if (!packed_launch_map(tile_order, n_tiles_, t_idx, wv, is_long)) return;   // four waves for the longest lists, else two
     int tile = t_idx;
     if (tile_order) tile = tile_order[tile];
     if constexpr (GROUPS) {
@@ -842,30 +728,9 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-// Transposed wave reduction of the nine per-Gaussian partial gradients (REDUCE == 1).  gfx950's
-// v_permlane32_swap / v_permlane16_swap exchange half-waves / odd-even rows BETWEEN two registers, so one swap +
-// one add folds two values at once: after the 32- and 16-lane stages three registers hold, per 16-lane row,
-// t0 = [v0 v2 v1 v3], t1 = [v4 v6 v5 v7], t2 = [v8 0 0 0]; four DPP adds finish each row.  28 cross-lane
-// ops instead of 54 shuffles.
-template <int CTRL>
-__device__ __forceinline__ float dpp_get(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float row_sum_dpp(float v) {   // every lane ends with its 16-lane row total
-    v += dpp_get<0xB1>(v);    // quad_perm:[1,0,3,2]
-    v += dpp_get<0x4E>(v);    // quad_perm:[2,3,0,1]
-    v += dpp_get<0x141>(v);   // row_half_mirror
-    v += dpp_get<0x140>(v);   // row_mirror
-    return v;
-}
-__device__ __forceinline__ float fold32(float a, float b) {   // lanes 0-31: a[l]+a[l+32]; lanes 32-63: same of b
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float fold16(float a, float b) {   // rows: [a.r0+a.r1, b.r0+b.r1, a.r2+a.r3, b.r2+b.r3]
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
+// The nine per-Gaussian partial gradients (REDUCE == 1) go through raster_common.h's transposed reduction: after the
+// 32- and 16-lane folds three registers hold, per 16-lane row, t0 = [v0 v2 v1 v3], t1 = [v4 v6 v5 v7], t2 = [v8 0 0 0];
+// four DPP adds finish each row.  28 cross-lane ops instead of 54 shuffles.
 
 // grad_ws row layout (12 floats / Gaussian): 0,1 m_x, m_y | 2,3,4 s_xx, s_xy, s_yy (raw moments; the conic is applied by
 // unpack_grads_kernel) | 5,6,7 v_rgb | 8 v_opacity
@@ -1030,67 +895,32 @@ __device__ __forceinline__ void raster_bwd_tile(int tile, int wv, int W, int H, 
         }
     };
 
-    const int L = kmax - range.x + 1;   // entries of the reverse walk
+    // the reverse walk, kmax down to range.x: the forward's two ways through the list, downwards
+    const int L = kmax - range.x + 1;
     if (L < batch_thresh) {
-        int idc = ids[kmax];                         // raw id word (quadrant bits on top)
-        Rec cur = recs[idc & idmask];
-        int idn = ids[max(kmax - 1, range.x)];
-        for (int k = kmax; k >= range.x; --k) {
-            const Rec nxt = recs[idn & idmask];
-            const int idnn = idn;
-            idn = ids[max(k - 2, range.x)];
-            entry(cur, k, qm_on ? qm_bits(idc, cur.ex) : quadrant_mask(cur, qcx, qcy, qtest));
-            cur = nxt;
-            idc = idnn;
-        }
+        walk_chase<-1, false>(ids, recs, nullptr, idmask, kmax, range.x, [&](const Rec &cur, int raw, int k, float) {
+            entry(cur, k, qm_on ? qm_bits(raw, cur.ex) : quadrant_mask(cur, qcx, qcy, qtest));
+            return true;
+        });
     } else {
-        // long walk: 64-entry batches staged through wave-private LDS (see the forward kernel)
         __shared__ float4 stage[2][64 * 3];
-        const int nb = (L + 63) >> 6;
-        int rid = 0;         // raw id word of this lane's row
-        auto fetch = [&](int bidx, float4 &r0, float4 &r1, float4 &r2) __attribute__((always_inline)) {
-            const int k = kmax - (bidx << 6) - lane;
-            if (k >= range.x) {
-                rid = ids[k];
-                const float4 *p = reinterpret_cast<const float4 *>(recs + (rid & idmask));
-                r0 = p[0]; r1 = p[1]; r2 = p[2];
-            }
-        };
-        auto row_mask = [&](const float4 &r0, const float4 &r2) __attribute__((always_inline)) -> unsigned {
-            return qm_on ? qm_bits(rid, r2.z) : row_quadrants(r0.x, r0.y, r2.z, r2.w, tx * 16, ty * 16, qtest);
-        };
         unsigned mine_q = 0u;
 #pragma unroll
         for (int q = 0; q < QPW; ++q)
             if (kfin_active[q]) mine_q |= 1u << (q0 + q);
-        float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0;
-        fetch(0, r0, r1, r2);
-        stage[0][lane * 3 + 0] = r0; stage[0][lane * 3 + 1] = r1; stage[0][lane * 3 + 2] = r2;
-        unsigned qrow = row_mask(r0, r2) & mine_q;
-        for (int bi = 0; bi < nb; ++bi) {
-            const int cnt = min(64, L - (bi << 6));
-            unsigned long long todo = __ballot(lane < cnt && qrow != 0u);
-            const unsigned qcur = qrow;
-            if (bi + 1 < nb) fetch(bi + 1, r0, r1, r2);
-            const float4 *sb = stage[bi & 1];
-            while (todo) {
-                const int j = __ffsll((long long)todo) - 1;
-                todo &= todo - 1;
-                Rec cur;
-                const float4 a0 = sb[j * 3 + 0], a1 = sb[j * 3 + 1], a2 = sb[j * 3 + 2];
-                cur.x = a0.x; cur.y = a0.y; cur.opac = a0.z; cur.ha = a0.w;
-                cur.b = a1.x; cur.hc = a1.y; cur.r = a1.z; cur.g = a1.w;
-                cur.bl = a2.x; cur.gid = __float_as_int(a2.y); cur.ex = a2.z; cur.ey = a2.w;
-                entry(cur, kmax - (bi << 6) - j, (unsigned)__builtin_amdgcn_readlane((int)qcur, j));
-            }
-            if (bi + 1 < nb) {
-                float4 *sn = stage[(bi + 1) & 1];
-                sn[lane * 3 + 0] = r0; sn[lane * 3 + 1] = r1; sn[lane * 3 + 2] = r2;
-                qrow = row_mask(r0, r2) & mine_q;
-            }
-        }
+        walk_staged<-1, false>(
+            ids, recs, nullptr, idmask, kmax, L, stage, nullptr,
+            [&](int raw, const float4 &r0, const float4 &r2) {
+                return (qm_on ? qm_bits(raw, r2.z) : row_quadrants(r0.x, r0.y, r2.z, r2.w, tx * 16, ty * 16, qtest)) & mine_q;
+            },
+            [](bool, int) {},
+            [&](const Rec &cur, int, int k, unsigned qm, float) {
+                entry(cur, k, qm);
+                return true;
+            });
     }
 }
+
 
 // Launch shapes of the backward.
 //   MODE 0: one workgroup per (tile, wave), the in-kernel adaptive split (QPW = 4, ADAPT): callers without a launch
@@ -1181,12 +1011,7 @@ __global__ __launch_bounds__(256) void unpack_grads_kernel(int n, int row0, cons
     const float4 a = reinterpret_cast<const float4 *>(ws)[3 * (size_t)(row0 + i) + 0];
     const float4 b = reinterpret_cast<const float4 *>(ws)[3 * (size_t)(row0 + i) + 1];
     const float4 c = reinterpret_cast<const float4 *>(ws)[3 * (size_t)(row0 + i) + 2];
-    // moments -> gradients with this Gaussian's conic: sigma = (A dx^2 + C dy^2) / 2 + B dx dy, so
-    //   v_xy = (A m_x + B m_y, B m_x + C m_y),  v_conic = (s_xx / 2, s_xy, s_yy / 2)  ([:,1] is the TRUE dL/dB)
-    const float A = conics[3 * i], B = conics[3 * i + 1], C = conics[3 * i + 2];
-    v_xy[2 * i] = fmaf(A, a.x, B * a.y);
-    v_xy[2 * i + 1] = fmaf(B, a.x, C * a.y);
-    v_conic[3 * i] = 0.5f * a.z; v_conic[3 * i + 1] = a.w; v_conic[3 * i + 2] = 0.5f * b.x;
+    moments_to_grads(conics + 3 * i, a, b.x, v_xy + 2 * i, v_conic + 3 * i);
     float v0 = b.y, v1 = b.z, v2 = b.w;
     if (colors_pre != nullptr) {   // the colours were clamp(pre, min = 0): gradient w.r.t. `pre` (torch: grad * (pre >= 0))
         v0 = colors_pre[3 * i] >= 0.f ? v0 : 0.f;
@@ -1225,21 +1050,9 @@ __global__ __launch_bounds__(64) void raster_views_fwd_kernel(int W, int H, int 
                                                               float *__restrict__ out_depth, int use_qm) {
     __shared__ float4 stage[2][64 * 3];
     __shared__ float stage_d[DEPTH ? 2 : 1][64];
-    const int n_long = min(max(tile_order[n_tiles_], 0), n_tiles_);
-    const int b_long = ((n_long + 7) >> 3) << 5;
-    const int b = (int)blockIdx.x;
     int t_idx, wv;
-    const bool is_long = b < b_long;
-    if (is_long) {
-        t_idx = (b >> 5) * 8 + (b & 7);
-        wv = (b >> 3) & 3;
-        if (t_idx >= n_long) return;
-    } else {
-        const int b2 = b - b_long;
-        t_idx = n_long + (b2 >> 4) * 8 + (b2 & 7);
-        wv = (b2 >> 3) & 1;
-        if (t_idx >= n_tiles_) return;
-    }
+    bool is_long;
+    if (!packed_launch_map(tile_order, n_tiles_, t_idx, wv, is_long)) return;
     const int tile = tile_order[t_idx];
     const int view = tile / tiles_per_view, lt = tile - view * tiles_per_view;
     const size_t px0 = (size_t)view * W * H;
@@ -1322,10 +1135,7 @@ __global__ __launch_bounds__(256) void unpack_views_kernel(int n, int n_views, c
         const float4 a = reinterpret_cast<const float4 *>(ws)[3 * r + 0];
         const float4 b = reinterpret_cast<const float4 *>(ws)[3 * r + 1];
         const float4 c = reinterpret_cast<const float4 *>(ws)[3 * r + 2];
-        const float A = conics[3 * r], B = conics[3 * r + 1], C = conics[3 * r + 2];
-        v_xy[2 * r] = fmaf(A, a.x, B * a.y);
-        v_xy[2 * r + 1] = fmaf(B, a.x, C * a.y);
-        v_conic[3 * r] = 0.5f * a.z; v_conic[3 * r + 1] = a.w; v_conic[3 * r + 2] = 0.5f * b.x;
+        moments_to_grads(conics + 3 * r, a, b.x, v_xy + 2 * r, v_conic + 3 * r);
         v_colors[3 * r] = b.y; v_colors[3 * r + 1] = b.z; v_colors[3 * r + 2] = b.w;
         vsum += c.x * sg * (1.f - sg);
     }

@@ -24,7 +24,8 @@
 // or bounding box (others) miss the tile's quadrants are never visited.  A visited entry's operands — its 32-byte
 // geometry row (x, y, activated opacity, ha | b, hc, ex, ey; built once per call in the workspace) and its CH
 // features — are fetched at the wave-uniform id, one entry ahead, and reach the VALU as uniform operands: no LDS, so
-// occupancy is set by registers alone.  Backward: the wave's partial sums (five moments, v_opacity, CH feature
+// occupancy is set by registers alone.  That traversal is walk_uniform below, upwards for the forward and downwards for
+// the backward; the two kernels supply what they do per entry.  Backward: the wave's partial sums (five moments, v_opacity, CH feature
 // gradients) are reduced with the transposed permlane-swap + DPP reduction of raster.hip, four values per result
 // register, and ONE global_atomic_add_f32 instruction with up to 22 active lanes adds them to the per-Gaussian geometry
 // row and straight into v_features.
@@ -49,14 +50,8 @@ __global__ __launch_bounds__(256) void feat_rows_kernel(int n, const float *__re
     const float a = conics[3 * g], b = conics[3 * g + 1], c = conics[3 * g + 2];
     float o = opac[g];
     if (opac_is_logit) o = 1.f / (1.f + expf(-o));
-    const float s = (o * 255.f > 0.f) ? logf(255.f * o) + 0.01f : -1.f;
-    const float D = a * c - b * b;
-    float ex = -1.f, ey = -1.f;
-    if (s >= 0.f) {
-        const bool proper = a > 0.f && c > 0.f && D > 0.f;
-        ex = proper ? sqrtf(2.f * s * c / D) + 1e-3f : 3.0e38f;
-        ey = proper ? sqrtf(2.f * s * a / D) + 1e-3f : 3.0e38f;
-    }
+    float ex, ey;
+    alpha_box(o, a, b, c, ex, ey);
     geo[2 * (size_t)g + 0] = make_float4(x, y, o, 0.5f * a);
     geo[2 * (size_t)g + 1] = make_float4(b, 0.5f * c, ex, ey);
 }
@@ -65,12 +60,6 @@ __global__ __launch_bounds__(256) void feat_rows_kernel(int n, const float *__re
 __device__ __forceinline__ void quad_pixel(int q, int lane, int tx, int ty, int &i, int &j) {
     j = tx * 16 + (q & 1) * 8 + (lane & 7);
     i = ty * 16 + (q >> 1) * 8 + (lane >> 3);
-}
-
-__device__ __forceinline__ int wave_max_int(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
-    return v;
 }
 
 // One visited entry's operands at the wave-uniform id `gid`: the geometry row and the chunk's CH features (channels past
@@ -106,6 +95,57 @@ __device__ __forceinline__ void fetch_id(const int32_t *__restrict__ ids, const 
         } else {
             const float4 g0 = geo[2 * (size_t)gid + 0], g1 = geo[2 * (size_t)gid + 1];
             qrow = row_quadrants(g0.x, g0.y, g1.z, g1.w, tx * 16, ty * 16, true);
+        }
+    }
+}
+
+// The walk of both kernels: `n` positions of the tile's list from `first` on, upwards (DIR = 1) or downwards (DIR = -1).
+// The ids (and boxes) of the next 64 positions are in flight while a batch is composited; a visited entry's operands
+// are fetched at its wave-uniform id while the entry before it is evaluated.  visit(g0, g1, f, gid, k, qm) gets the
+// entry at list position k and the tile's quadrants qm it can touch; false stops the walk.
+template <int DIR, int CH, class Visit>
+__device__ __forceinline__ void walk_uniform(const int32_t *__restrict__ ids, const float4 *__restrict__ geo,
+                                             const float *__restrict__ feats, int K, int c0, int nvalid, int use_qm,
+                                             int idmask, int tx, int ty, int first, int n, Visit visit) {
+    const int lane = threadIdx.x;
+    int gidv, gidv_n = 0;
+    unsigned qrow, qrow_n = 0u;
+    if (n > 0) fetch_id(ids, geo, first + DIR * lane, lane < n, use_qm, idmask, tx, ty, gidv_n, qrow_n);
+    bool go = true;
+    for (int b0 = 0; b0 < n && go; b0 += 64) {
+        gidv = gidv_n;
+        qrow = qrow_n;
+        if (b0 + 64 < n)
+            fetch_id(ids, geo, first + DIR * (b0 + 64 + lane), b0 + 64 + lane < n, use_qm, idmask, tx, ty, gidv_n, qrow_n);
+        unsigned long long todo = __ballot(qrow != 0u);
+        if (todo == 0ull) continue;
+        int j = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        unsigned qm = (unsigned)__builtin_amdgcn_readlane((int)qrow, j);
+        int gid = __builtin_amdgcn_readlane(gidv, j);
+        float4 g0, g1;
+        float f[CH];
+        load_entry<CH>(geo, feats, gid, K, c0, nvalid, g0, g1, f);
+        while (true) {
+            const bool more = todo != 0ull;       // wave-uniform
+            int jn = j, gidn = gid;
+            unsigned qmn = qm;
+            float4 n0 = g0, n1 = g1;
+            float fn[CH];
+#pragma unroll
+            for (int c = 0; c < CH; ++c) fn[c] = f[c];
+            if (more) {                            // the next visited entry's operands, one entry ahead
+                jn = __ffsll((long long)todo) - 1;
+                todo &= todo - 1;
+                qmn = (unsigned)__builtin_amdgcn_readlane((int)qrow, jn);
+                gidn = __builtin_amdgcn_readlane(gidv, jn);
+                load_entry<CH>(geo, feats, gidn, K, c0, nvalid, n0, n1, fn);
+            }
+            if (!visit(g0, g1, f, gid, first + DIR * (b0 + j), qm)) { go = false; break; }
+            if (!more) break;
+            j = jn; gid = gidn; qm = qmn; g0 = n0; g1 = n1;
+#pragma unroll
+            for (int c = 0; c < CH; ++c) f[c] = fn[c];
         }
     }
 }
@@ -173,45 +213,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH == 16 ? 4
         return true;
     };
 
-    const int L = range.y - range.x;
-    int gidv, gidv_n = 0;
-    unsigned qrow, qrow_n = 0u;
-    if (L > 0) fetch_id(ids, geo, range.x + lane, lane < L, use_qm, idmask, tx, ty, gidv_n, qrow_n);
-    bool go = true;
-    for (int b0 = 0; b0 < L && go; b0 += 64) {
-        gidv = gidv_n;
-        qrow = qrow_n;
-        if (b0 + 64 < L)   // the next batch's ids (and boxes) are in flight while this one is composited
-            fetch_id(ids, geo, range.x + b0 + 64 + lane, b0 + 64 + lane < L, use_qm, idmask, tx, ty, gidv_n, qrow_n);
-        unsigned long long todo = __ballot(qrow != 0u);
-        if (todo == 0ull) continue;
-        int j = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        unsigned qm = (unsigned)__builtin_amdgcn_readlane((int)qrow, j);
-        float4 g0, g1;
-        float f[CH];
-        load_entry<CH>(geo, feats, __builtin_amdgcn_readlane(gidv, j), K, c0, nvalid, g0, g1, f);
-        while (true) {
-            const bool more = todo != 0ull;       // wave-uniform
-            int jn = j;
-            unsigned qmn = qm;
-            float4 n0 = g0, n1 = g1;
-            float fn[CH];
-#pragma unroll
-            for (int c = 0; c < CH; ++c) fn[c] = f[c];
-            if (more) {                            // the next visited entry's operands, one entry ahead
-                jn = __ffsll((long long)todo) - 1;
-                todo &= todo - 1;
-                qmn = (unsigned)__builtin_amdgcn_readlane((int)qrow, jn);
-                load_entry<CH>(geo, feats, __builtin_amdgcn_readlane(gidv, jn), K, c0, nvalid, n0, n1, fn);
-            }
-            if (!entry(g0, g1, f, range.x + b0 + j, qm)) { go = false; break; }
-            if (!more) break;
-            j = jn; qm = qmn; g0 = n0; g1 = n1;
-#pragma unroll
-            for (int c = 0; c < CH; ++c) f[c] = fn[c];
-        }
-    }
+    walk_uniform<1, CH>(ids, geo, feats, K, c0, nvalid, use_qm, idmask, tx, ty, range.x, range.y - range.x,
+                        [&](const float4 &g0, const float4 &g1, const float (&f)[CH], int, int k, unsigned qm) {
+                            return entry(g0, g1, f, k, qm);
+                        });
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         int i, j;
@@ -231,29 +236,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH == 16 ? 4
 }
 
 // ------------------------------------------------------------------ backward
-// transposed wave reduction (raster.hip): permlane32_swap / permlane16_swap fold two registers per swap, DPP adds
-// finish the 16-lane rows.  reduce4(a, b, c, d): rows 0, 1, 2, 3 of the result hold the wave totals of a, c, b, d.
-template <int CTRL>
-__device__ __forceinline__ float f_dpp(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float f_fold32(float a, float b) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float f_fold16(float a, float b) {
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float reduce4(float a, float b, float c, float d) {
-    float v = f_fold16(f_fold32(a, b), f_fold32(c, d));
-    v += f_dpp<0xB1>(v);    // quad_perm:[1,0,3,2]
-    v += f_dpp<0x4E>(v);    // quad_perm:[2,3,0,1]
-    v += f_dpp<0x141>(v);   // row_half_mirror
-    v += f_dpp<0x140>(v);   // row_mirror
-    return v;
-}
-
+// (the wave's partial sums go through raster_common.h's transposed reduction: reduce4(a, b, c, d) leaves the wave totals
+// of a, c, b, d in rows 0, 1, 2, 3)
 constexpr int GW_FLOATS = 8;   // per-Gaussian geometry sums: m_x m_y s_xx s_xy | s_yy v_opacity 0 0
 
 template <bool EXACT, int CH>
@@ -288,7 +272,7 @@ __global__ __launch_bounds__(64) void feat_bwd_kernel(int W, int H, int tiles_x,
         kfin[q] = inside ? final_idx[pixi[q]] : -1;   // -1: this slot never participates
         kmax_l = max(kmax_l, kfin[q]);
     }
-    int kmax = __builtin_amdgcn_readfirstlane(wave_max_int(kmax_l));
+    int kmax = __builtin_amdgcn_readfirstlane(wave_max_i(kmax_l));
     kmax = min(kmax, range.y - 1);
     if (kmax < range.x) return;
 #pragma unroll
@@ -376,46 +360,11 @@ __global__ __launch_bounds__(64) void feat_bwd_kernel(int W, int H, int tiles_x,
         }
     };
 
-    const int L = kmax - range.x + 1;   // entries of the reverse walk
-    int gidv, gidv_n = 0;
-    unsigned qrow, qrow_n = 0u;
-    fetch_id(ids, geo, kmax - lane, lane < L, use_qm, idmask, tx, ty, gidv_n, qrow_n);
-    for (int b0 = 0; b0 < L; b0 += 64) {
-        gidv = gidv_n;
-        qrow = qrow_n;
-        if (b0 + 64 < L)
-            fetch_id(ids, geo, kmax - b0 - 64 - lane, b0 + 64 + lane < L, use_qm, idmask, tx, ty, gidv_n, qrow_n);
-        unsigned long long todo = __ballot(qrow != 0u);
-        if (todo == 0ull) continue;
-        int j = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        unsigned qm = (unsigned)__builtin_amdgcn_readlane((int)qrow, j);
-        int gid = __builtin_amdgcn_readlane(gidv, j);
-        float4 g0, g1;
-        float f[CH];
-        load_entry<CH>(geo, feats, gid, K, c0, nvalid, g0, g1, f);
-        while (true) {
-            const bool more = todo != 0ull;       // wave-uniform
-            int jn = j, gidn = gid;
-            unsigned qmn = qm;
-            float4 n0 = g0, n1 = g1;
-            float fn[CH];
-#pragma unroll
-            for (int c = 0; c < CH; ++c) fn[c] = f[c];
-            if (more) {
-                jn = __ffsll((long long)todo) - 1;
-                todo &= todo - 1;
-                qmn = (unsigned)__builtin_amdgcn_readlane((int)qrow, jn);
-                gidn = __builtin_amdgcn_readlane(gidv, jn);
-                load_entry<CH>(geo, feats, gidn, K, c0, nvalid, n0, n1, fn);
-            }
-            entry(g0, g1, f, gid, kmax - b0 - j, qm);
-            if (!more) break;
-            j = jn; gid = gidn; qm = qmn; g0 = n0; g1 = n1;
-#pragma unroll
-            for (int c = 0; c < CH; ++c) f[c] = fn[c];
-        }
-    }
+    walk_uniform<-1, CH>(ids, geo, feats, K, c0, nvalid, use_qm, idmask, tx, ty, kmax, kmax - range.x + 1,
+                         [&](const float4 &g0, const float4 &g1, const float (&f)[CH], int gid, int k, unsigned qm) {
+                             entry(g0, g1, f, gid, k, qm);
+                             return true;
+                         });
 }
 
 // per-Gaussian geometry sums -> v_xy, v_conic, v_opacity (unpack_grads_kernel of raster.hip without the colours)
@@ -428,14 +377,7 @@ __global__ __launch_bounds__(256) void feat_unpack_kernel(int n, const float *__
     if (i >= n) return;
     const float4 a = reinterpret_cast<const float4 *>(gws)[2 * (size_t)i + 0];
     const float4 b = reinterpret_cast<const float4 *>(gws)[2 * (size_t)i + 1];
-    // sigma = (A dx^2 + C dy^2) / 2 + B dx dy:  v_xy = (A m_x + B m_y, B m_x + C m_y),
-    // v_conic = (s_xx / 2, s_xy, s_yy / 2)  ([:,1] is the TRUE dL/dB)
-    const float A = conics[3 * (size_t)i], B = conics[3 * (size_t)i + 1], C = conics[3 * (size_t)i + 2];
-    v_xy[2 * (size_t)i] = fmaf(A, a.x, B * a.y);
-    v_xy[2 * (size_t)i + 1] = fmaf(B, a.x, C * a.y);
-    v_conic[3 * (size_t)i] = 0.5f * a.z;
-    v_conic[3 * (size_t)i + 1] = a.w;
-    v_conic[3 * (size_t)i + 2] = 0.5f * b.x;
+    moments_to_grads(conics + 3 * (size_t)i, a, b.x, v_xy + 2 * (size_t)i, v_conic + 3 * (size_t)i);
     float vo = b.y;
     if (opac_is_logit) {              // opac holds logits: chain through the fused sigmoid
         const float sg = 1.f / (1.f + expf(-opac[i]));

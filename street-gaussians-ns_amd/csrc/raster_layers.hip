@@ -15,7 +15,8 @@
 //
 // Shape of the launch: that of the packed forward — the first tile_order[n_tiles] tiles of the launch order (the longest
 // lists) get four waves, one 8x8 quadrant each, the others two waves with a 16x8 half each — and the same two ways
-// through a list (scalar chase one entry ahead; 64-entry batches staged in wave-private LDS from batch_fwd entries on).
+// through a list (scalar chase one entry ahead; 64-entry batches staged in wave-private LDS from batch_fwd entries on:
+// raster_common.h's walk_chase / walk_staged and its packed_launch_map, the very source the packed forward runs).
 // The walk of the shared list goes on while the all-layer or the head layer is alive.  The tail layer — a few objects
 // in front of a saturated background never finish — goes on along ITS OWN compacted list (sgn_list_window) from where
 // the shared walk left it, as the GROUPS forward does; without such a list it keeps the shared walk alive instead.
@@ -147,107 +148,49 @@ __device__ __forceinline__ void layers_tile(const LayerArgs &A, int tile, int wv
 
     int cO = 0;      // tail entries of the shared list met so far
     int rO = -1;     // ... when the shared walk stopped early (-1: it reached the end of the list)
+    auto box_mask = [&](int raw, const Rec &cur) __attribute__((always_inline)) -> unsigned {
+        return qm_on ? qm_bits(raw, cur.ex) : quadrant_mask(cur, qcx, qcy, true);
+    };
     const int L = range.y - range.x;
-    if (L > 0 && L < A.batch_thresh) {
-        // short list: chase ids -> rows with scalar loads, one entry ahead (operands arrive in SGPRs)
-        int idc = A.ids[range.x];
-        Rec cur = A.recs[idc & idmask];
-        float dcur = A.depths[idc & idmask];
-        int idn = A.ids[min(range.x + 1, range.y - 1)];
-        for (int k = range.x; k < range.y; ++k) {
-            const Rec nxt = A.recs[idn & idmask];
-            const float dnxt = A.depths[idn & idmask];
-            const int idnn = idn;
-            idn = A.ids[min(k + 2, range.y - 1)];
-            const unsigned qm = qm_on ? qm_bits(idc, cur.ex) : quadrant_mask(cur, qcx, qcy, true);
-            const bool tail = LAYERS && (idc & idmask) >= split;
-            if (!entry(cur, qm, dcur, tail, false)) { rO = cO; break; }   // this entry is still to come
+    if (L < A.batch_thresh) {
+        walk_chase<1, true>(A.ids, A.recs, A.depths, idmask, range.x, range.y - 1, [&](const Rec &cur, int raw, int, float dep) {
+            const bool tail = LAYERS && (raw & idmask) >= split;
+            if (!entry(cur, box_mask(raw, cur), dep, tail, false)) { rO = cO; return false; }   // this entry is still to come
             cO += (int)tail;
-            cur = nxt;
-            dcur = dnxt;
-            idc = idnn;
-        }
-    } else if (L > 0) {
-        // long list: 64-entry batches through wave-private LDS (raster.hip raster_fwd_tile; no barrier: one wave)
-        const int nb = (L + 63) >> 6;
-        float rd = 0.f;
-        int rid = 0;
-        auto fetch = [&](int bidx, float4 &r0, float4 &r1, float4 &r2) __attribute__((always_inline)) {
-            const int k = range.x + (bidx << 6) + lane;
-            if (k < range.y) {
-                rid = A.ids[k];
-                const int id = rid & idmask;
-                const float4 *p = reinterpret_cast<const float4 *>(A.recs + id);
-                r0 = p[0]; r1 = p[1]; r2 = p[2];
-                rd = A.depths[id];
-            }
-        };
-        auto row_mask = [&](const float4 &r0, const float4 &r2) __attribute__((always_inline)) -> unsigned {
-            return qm_on ? qm_bits(rid, r2.z) : row_quadrants(r0.x, r0.y, r2.z, r2.w, tx * 16, ty * 16, true);
-        };
+            return true;
+        });
+    } else {
         unsigned mine_q = 0u;
 #pragma unroll
         for (int q = 0; q < QPW; ++q) mine_q |= 1u << (q0 + q);
-        float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0;
-        fetch(0, r0, r1, r2);
-        stage[0][lane * 3 + 0] = r0; stage[0][lane * 3 + 1] = r1; stage[0][lane * 3 + 2] = r2;
-        stage_d[0][lane] = rd;
-        unsigned qrow = row_mask(r0, r2) & mine_q;
-        bool trow = LAYERS && (rid & idmask) >= split;
-        bool go = true;
-        for (int bi = 0; bi < nb && go; ++bi) {
-            const int cnt = min(64, L - (bi << 6));
-            unsigned long long todo = __ballot(lane < cnt && qrow != 0u);
-            const unsigned long long tmask = LAYERS ? __ballot(lane < cnt && trow) : 0ull;
-            const unsigned qcur = qrow;
-            if (bi + 1 < nb) fetch(bi + 1, r0, r1, r2);
-            const float4 *sb = stage[bi & 1];
-            while (todo) {
-                const int j = __ffsll((long long)todo) - 1;
-                todo &= todo - 1;
-                Rec cur;
-                const float4 a0 = sb[j * 3 + 0], a1 = sb[j * 3 + 1], a2 = sb[j * 3 + 2];
-                cur.x = a0.x; cur.y = a0.y; cur.opac = a0.z; cur.ha = a0.w;
-                cur.b = a1.x; cur.hc = a1.y; cur.r = a1.z; cur.g = a1.w;
-                cur.bl = a2.x; cur.gid = __float_as_int(a2.y); cur.ex = a2.z; cur.ey = a2.w;
-                const unsigned qm = (unsigned)__builtin_amdgcn_readlane((int)qcur, j);
-                const float dep = stage_d[bi & 1][j];
-                const bool tail = (tmask >> j) & 1ull;
-                if (!entry(cur, qm, dep, tail, false)) {
-                    rO = cO + __popcll(tmask & ((1ull << j) - 1ull));
-                    go = false;
-                    break;
+        unsigned long long tmask = 0ull;   // the batch's tail entries
+        int cB = 0;                        // tail entries before the batch
+        walk_staged<1, true>(
+            A.ids, A.recs, A.depths, idmask, range.x, L, stage, stage_d,
+            [&](int raw, const float4 &r0, const float4 &r2) {
+                return (qm_on ? qm_bits(raw, r2.z) : row_quadrants(r0.x, r0.y, r2.z, r2.w, tx * 16, ty * 16, true)) & mine_q;
+            },
+            [&](bool in_batch, int raw) {
+                if constexpr (LAYERS) {
+                    tmask = __ballot(in_batch && (raw & idmask) >= split);
+                    cB = cO;
+                    cO += __popcll(tmask);
                 }
-            }
-            cO += __popcll(tmask);
-            if (go && bi + 1 < nb) {
-                float4 *sn = stage[(bi + 1) & 1];
-                sn[lane * 3 + 0] = r0; sn[lane * 3 + 1] = r1; sn[lane * 3 + 2] = r2;
-                stage_d[(bi + 1) & 1][lane] = rd;
-                qrow = row_mask(r0, r2) & mine_q;
-                trow = LAYERS && (rid & idmask) >= split;
-            }
-        }
+            },
+            [&](const Rec &cur, int j, int, unsigned qm, float dep) {
+                if (entry(cur, qm, dep, (tmask >> j) & 1ull, false)) return true;
+                rO = cB + __popcll(tmask & ((1ull << j) - 1ull));
+                return false;
+            });
     }
     if constexpr (LAYERS) {
         if (own) {
-            // the tail layer outlived the shared walk: the rest of its own list (scalar chase, one entry ahead)
+            // the tail layer outlived the shared walk: the rest of its own list
             const int2 ob = A.own_bins[tile];
-            const int from = ob.x + (rO < 0 ? cO : rO), end = ob.y;
-            if (from < end) {
-                int idc = A.own_ids[from];
-                Rec cur = A.recs[idc & idmask];
-                int idn = A.own_ids[min(from + 1, end - 1)];
-                for (int p = from; p < end; ++p) {
-                    const Rec nxt = A.recs[idn & idmask];
-                    const int idnn = idn;
-                    idn = A.own_ids[min(p + 2, end - 1)];
-                    const unsigned qm = qm_on ? qm_bits(idc, cur.ex) : quadrant_mask(cur, qcx, qcy, true);
-                    if (!entry(cur, qm, 0.f, true, true)) break;
-                    cur = nxt;
-                    idc = idnn;
-                }
-            }
+            const int from = ob.x + (rO < 0 ? cO : rO);
+            walk_chase<1, false>(A.own_ids, A.recs, nullptr, idmask, from, ob.y - 1, [&](const Rec &cur, int raw, int, float) {
+                return entry(cur, box_mask(raw, cur), 0.f, true, true);
+            });
         }
     }
     const size_t HW = (size_t)W * (size_t)H;
@@ -287,23 +230,9 @@ template <bool EXACT>
 __global__ __launch_bounds__(64) void raster_layers_kernel(const LayerArgs A) {
     __shared__ float4 stage[2][64 * 3];
     __shared__ float stage_d[2][64];
-    // block -> (tile, wave) as raster.hip's raster_fwd_pk_kernel: the n_long longest lists of the launch order get four
-    // waves each, the others two, in groups of eight tiles so that a tile's waves share an XCD
-    const int n_long = A.tile_order ? min(max(A.tile_order[A.n_tiles], 0), A.n_tiles) : 0;
-    const int b_long = ((n_long + 7) >> 3) << 5;
-    const int b = (int)blockIdx.x;
     int t_idx, wv;
-    const bool is_long = b < b_long;
-    if (is_long) {
-        t_idx = (b >> 5) * 8 + (b & 7);
-        wv = (b >> 3) & 3;
-        if (t_idx >= n_long) return;
-    } else {
-        const int b2 = b - b_long;
-        t_idx = n_long + (b2 >> 4) * 8 + (b2 & 7);
-        wv = (b2 >> 3) & 1;
-        if (t_idx >= A.n_tiles) return;
-    }
+    bool is_long;
+    if (!packed_launch_map(A.tile_order, A.n_tiles, t_idx, wv, is_long)) return;
     int tile = t_idx;
     if (A.tile_order) tile = A.tile_order[tile];
     if (tile < 0 || tile >= A.n_tiles) return;
