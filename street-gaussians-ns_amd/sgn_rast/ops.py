@@ -1336,22 +1336,17 @@ def _list_window(ids: torch.Tensor, tile_bins: torch.Tensor, lo: int, hi: int, q
 
 
 # ------------------------------------------------------------ depth channel
-# The reference renders depth with a SECOND full rasterization of the same geometry, the colours being the depths
-# themselves (sgn_splatfacto.py:982-994).  The forward kernels can accumulate that image as a fourth channel of the
-# FIRST pass (one fma per evaluated pair), and the second call is then answered from it: a device-side comparison proves
-# that its colours are `depths.repeat(1, 3)`, the ordinary forward is queued behind a flag that turns its kernels into
-# no-ops, and one small kernel writes the image and the per-pixel state the second node's backward needs
-# (sgn_depth_reuse) — no host sync, bit-equal to the two-pass result in exact-exp mode.
-# "auto" (default): the first pass starts accumulating once a step has been seen to make that second call (a rasterize
-# call on the very tensors of the previous one with other colours), and stops again when the calls stop coming;
-# "on" / "off" force it.  The fused API asks for the channel explicitly (rasterize_gaussians_fused(depth_channel=True)).
+# The reference's second rasterization of the same geometry with the depths as colours (sgn_splatfacto.py:982-994) is
+# answered from a fourth channel the FIRST pass accumulates (stage 3).  "auto" (default): accumulate once a
+# step has been seen to make that second call, stop when the calls stop coming; "on" / "off" force it.  The fused API asks
+# for the channel explicitly (rasterize_gaussians_fused(depth_channel=True)).
 depth_channel = config.value("depth_channel")
 depth_stats = {"accumulated": 0, "reused": 0, "proved_on_host": 0}
 group_stats = {"passes": 0, "backward_passes": 0}    # forwards that carried the two group accumulations; their backwards
 
 
-def _depth_wanted() -> bool:
-    return depth_channel == "on" or (depth_channel == "auto" and _S().depth_state["want"])
+def _depth_wanted(S=None) -> bool:
+    return depth_channel == "on" or (depth_channel == "auto" and (S or _S()).depth_state["want"])
 
 
 _provably_depths = proofs.repeated_depths     # host-side proof that colours are `depths[:, None].repeat(1, 3)` (:988)
@@ -1421,24 +1416,66 @@ _call_state = threading.local()
 # One library call per autograd node (round 5).  `sgn_rasterize_fwd_all` runs the forward's whole
 # launch sequence — first half of the binning, count read-back, rows, speculative second half, the wait, launch order,
 # forward kernels — behind ONE ctypes call with ONE arena for its temporaries, instead of six calls and a dozen
-# allocations driven from here.  It serves the plain case (the full scene, a fresh binning, no depth channel / reuse /
-# window / groups, a capacity known from earlier calls of the same shape); everything else, and a capacity miss, takes the
-# call-by-call path below, which stays the reference for behaviour.  Same kernels, same order, same results.
-# Option `one_call_nodes` (sgn_rast/config.py) switches it off.
+# allocations driven from here (which calls it serves: the route table of DESIGN.md 4.1).  Same kernels, same order, same
+# results as the call-by-call route, the reference for behaviour; option `one_call_nodes` switches it off.
 composite_forward = bool(config.value("one_call_nodes"))
 composite_backward = composite_forward      # the node's backward as one call too (sgn_rasterize_bwd_all, round 6)
 composite_stats = {"forwards": 0, "capacity_misses": 0, "windows": 0, "backwards": 0}
 _E_CAPACITY = -100
 
 
-def _forward_composite(S, key, _t, cull, n, xys_c, depths, radii, conics_c, colors_c, opac_c, opacity_is_logit,
-                       img_height, img_width, block_width, tile_bounds, bg_c, out_img, final_Ts, final_idx, ro, ro_ptr,
-                       logit_leaves, stream_ptr, out_depth=None):
-    """(num_intersects, ids, tile_bins, order, tile_kmax, rows) or None (no capacity known yet / the list did not fit:
-    the caller takes the call-by-call path)."""
+class _RasterCall:
+    """One rasterize forward's record, built once; a route unpacks the groups it needs into locals once.
+    src: the caller's tensors; dev_in: (xys_c, conics_c, colors_c, opac_c, bg_c); size: (n, H, W, block, tile_bounds);
+    outs: (out_img, final_Ts, final_idx), replaced where a pass drew nothing itself; span: (id_lo, id_hi, window, n_full)."""
+    __slots__ = ("src", "dev_in", "size", "outs", "span", "cull", "opacity_is_logit", "key", "_t", "logit_leaves", "ro",
+                 "ro_ptr", "stream_ptr", "dev", "out_depth", "hit", "ranged", "dcache", "depths_c", "skip_flag", "groups")
+
+    def __init__(self, xys, depths, radii, conics, num_tiles_hit, colors, opacity, img_height, img_width, block_width,
+                 background, opacity_is_logit, logit_leaves):
+        dev = self.dev = L.require_device(xys, depths, radii, conics, num_tiles_hit, colors, opacity, background)
+        if colors.shape[-1] != 3:
+            raise NotImplementedError(
+                "only the 3-channel rasterize path is implemented (the reference never uses N-D colours: "
+                "sgn_splatfacto.py:988 repeats depth x3 to stay on it)")
+        n = xys.size(0)
+        tile_bounds = ((img_width + block_width - 1) // block_width, (img_height + block_width - 1) // block_width, 1)
+        self.src = (xys, depths, radii, num_tiles_hit, conics, opacity)
+        self.size, self.span = (n, img_height, img_width, block_width, tile_bounds), (0, n, 0, n)
+        self.dev_in = (_f32c(xys), _f32c(conics), _f32c(colors), _f32c(opacity).reshape(-1), _f32c(background))
+        self.opacity_is_logit, self.logit_leaves = opacity_is_logit, logit_leaves
+        self.ro = L.opts().copy()         # this call's kernel options: the backward runs with the same ones
+        self.ro_ptr = C.byref(self.ro)
+        # everything that does not depend on the intersection count is prepared BEFORE the binning's host sync: the
+        # GPU idles from the moment the count is known until the next launch arrives, so that window is kept short
+        self.outs = (torch.empty(img_height, img_width, 3, dtype=torch.float32, device=dev),
+                     torch.empty(img_height, img_width, dtype=torch.float32, device=dev),
+                     torch.empty(img_height, img_width, dtype=torch.int32, device=dev))
+        self.out_depth = self.dcache = self.depths_c = self.skip_flag = self.groups = None
+        self.stream_ptr = L.stream_ptr()
+        self.key, self._t, self.cull = _cache_key(xys, depths, radii, num_tiles_hit, tile_bounds, block_width, conics,
+                                                  opacity, opacity_is_logit)
+
+
+def _forward_rows(call, n_full, num_intersects=0):
+    """The per-Gaussian rows workspace of a forward (one row per Gaussian of the scene its list was binned for)."""
+    return L.workspace(L.load().sgn_raster_workspace_bytes(n_full, num_intersects, call.ro_ptr), call.dev)
+
+
+# The routes of a rasterize forward (DESIGN.md 4.1); every route function returns
+# (route, num_intersects, ids, tile_bins, order, tile_kmax, rows).
+_WINDOW, _FRESH, _PROVEN, _NOTHING, _GROUPS, _PLAIN = "window", "fresh", "proven", "nothing", "groups", "plain"
+
+
+def _forward_composite(S, call):
+    """The one-call fresh route, or None (no capacity known yet / the list did not fit: the call-by-call route runs)."""
+    _xys, depths, radii, _nth, _conics, _opacity = call.src
     if not speculative_binning or depths.dtype is not torch.float32 or radii.dtype is not torch.int32:
         return None
-    dev = xys_c.device
+    n, img_height, img_width, block_width, tile_bounds = call.size
+    xys_c, conics_c, colors_c, opac_c, bg_c = call.dev_in
+    out_img, final_Ts, final_idx = call.outs
+    dev, ro, cull = call.dev, call.ro, call.cull
     tx, ty = int(tile_bounds[0]), int(tile_bounds[1])
     ckey = (dev, n, tx, ty, int(block_width))
     last = S.last_count.get(ckey, 0)
@@ -1455,7 +1492,7 @@ def _forward_composite(S, key, _t, cull, n, xys_c, depths, radii, conics_c, colo
     bins_and_stats = torch.empty(2, n_tiles, 2, **i32)
     tile_bins, tile_kmax = bins_and_stats[0], bins_and_stats[1]
     order = torch.empty(n_tiles + 2, **i32)
-    rows = L.workspace(lib.sgn_raster_workspace_bytes(n, 0, ro_ptr), dev)
+    rows = _forward_rows(call, n)
     arena = L.workspace(lib.sgn_rasterize_arena_bytes(n, cap), dev)
     scratch = _order_scratch(S, lib, n_tiles, dev)
     early_entry = S.early["entry"]
@@ -1470,13 +1507,12 @@ def _forward_composite(S, key, _t, cull, n, xys_c, depths, radii, conics_c, colo
     n_host = C.c_int64(0)
     rc = lib.sgn_rasterize_fwd_all(
         n, L.ptr(xys_c), L.ptr(_f32c(depths)), L.ptr(_i32c(radii)), L.ptr(conics_c), L.ptr(colors_c), L.ptr(opac_c),
-        int(bool(opacity_is_logit)), int(bool(cull)), int(img_height), int(img_width), int(block_width), L.ptr(bg_c),
-        L.ptr(early), int(qmask), L.ptr(out_img), L.ptr(final_Ts), L.ptr(final_idx), L.ptr(out_depth), L.ptr(ids), cap,
-        L.ptr(tile_bins),
-        L.ptr(order), L.ptr(tile_kmax), L.ptr(rows), rows.numel(), L.ptr(scratch),
+        int(bool(call.opacity_is_logit)), int(bool(cull)), int(img_height), int(img_width), int(block_width), L.ptr(bg_c),
+        L.ptr(early), int(qmask), L.ptr(out_img), L.ptr(final_Ts), L.ptr(final_idx), L.ptr(call.out_depth), L.ptr(ids),
+        cap, L.ptr(tile_bins), L.ptr(order), L.ptr(tile_kmax), L.ptr(rows), rows.numel(), L.ptr(scratch),
         4 * scratch.numel() if scratch is not None else 0, L.ptr(arena), arena.numel(), pinned[0:1].data_ptr(),
         L.ptr(walk_stat), pinned[7:8].data_ptr() if walk_stat is not None else None, C.byref(n_host),
-        L.sort_rank_mode(), semantics().flags(), ro_ptr, stream_ptr)
+        L.sort_rank_mode(), semantics().flags(), call.ro_ptr, call.stream_ptr)
     if walk_stat is not None and rc in (0, _E_CAPACITY):
         S.walked_permille = quadrant_mask_stats["walked_permille"] = int(pinned[7])
     count = int(n_host.value)
@@ -1500,12 +1536,14 @@ def _forward_composite(S, key, _t, cull, n, xys_c, depths, radii, conics_c, colo
     quadrant_mask_stats["binnings_with_masks"] += int(qmask)
     ro.ids_qmask = int(qmask)
     if count < 1:
-        return count, ids, tile_bins, order, tile_kmax, None
+        return _FRESH, count, ids, tile_bins, order, tile_kmax, None
     if binning_cache_enabled:
-        S.store_binning(key, tuple(t.detach() for t in _t), (count, ids, tile_bins), _window_info(_t, cull, logit_leaves))
+        _t = call._t
+        S.store_binning(call.key, tuple(t.detach() for t in _t), (count, ids, tile_bins),
+                        _window_info(_t, cull, call.logit_leaves))
     if tile_order_enabled:
         _remember_order(S, tile_bins, _fwd_long_thresh(ro, block_width), order)
-    return count, ids, tile_bins, order, tile_kmax, rows
+    return _FRESH, count, ids, tile_bins, order, tile_kmax, rows
 
 
 def _remember_order(S, tile_bins, long_thresh, order):
@@ -1553,17 +1591,16 @@ def _window_candidate(S, key_tail, n, mine):
     return sorted({0, n_full - n}), val, keep
 
 
-def _forward_window_composite(S, cand, n, xys_c, depths, radii, num_tiles_hit, conics_c, colors_c, opac_c,
-                              opacity_is_logit, cull, img_height, img_width, block_width, bg_c, out_img, final_Ts,
-                              final_idx, ro, ro_ptr, stream_ptr):
-    """ONE library call for a sub-model pass over the cached list (sgn_rasterize_window_all, round 6): the device-side
-    comparison of all six tensors at the head / tail offsets, the verdict's read-back, the window's rows, its sub-list,
-    the launch order and the forward kernels.  -> (lo, n_full, num_intersects, ids, bins, order, tile_kmax, rows) or None
-    (not a window of that scene: the caller bins the tensors themselves)."""
+def _forward_window_composite(S, call, cand):
+    """The one-call window route (sgn_rasterize_window_all, round 6): the device-side comparison of all six tensors at the
+    head / tail offsets, the verdict's read-back, the window's rows, its sub-list, the launch order and the forward
+    kernels.  -> ((lo, None, n_full), the route's tuple) or None (not a window of that scene: the tensors are binned)."""
     cands, (num_intersects, ids_full, bins_full), keep = cand
-    n_full = keep[0].shape[0]
-    dev = xys_c.device
-    lib = L.load()
+    _xys, depths, radii, num_tiles_hit, _conics, _opacity = call.src
+    n, img_height, img_width, block_width, _bounds = call.size
+    xys_c, conics_c, colors_c, opac_c, bg_c = call.dev_in
+    out_img, final_Ts, final_idx = call.outs
+    n_full, dev, ro, lib = keep[0].shape[0], call.dev, call.ro, L.load()
     i32 = dict(dtype=torch.int32, device=dev)
     n_tiles = bins_full.shape[0]
     qmask = int(bool(getattr(ids_full, "_sgn_qmask", False)))
@@ -1578,25 +1615,25 @@ def _forward_window_composite(S, cand, n, xys_c, depths, radii, num_tiles_hit, c
     bins_out = torch.empty_like(bins_full) if sub else None
     order = torch.empty(n_tiles + 2, **i32) if order_ready is None else None
     tile_kmax = torch.empty(n_tiles, 2, **i32)
-    rows = L.workspace(lib.sgn_raster_workspace_bytes(n_full, 0, ro_ptr), dev)
+    rows = _forward_rows(call, n_full)
     arena = L.workspace(lib.sgn_rasterize_window_arena_bytes(n_tiles), dev)
     scratch = _order_scratch(S, lib, n_tiles, dev)
     pinned = _side_row(S)
     f = [c if c.is_contiguous() else c.contiguous() for c in keep] + [None] * (6 - len(keep))
-    if cull:
+    if call.cull:
         f[5] = f[5].reshape(-1)
     lo_host = (C.c_int32 * len(cands))(*cands)
     matched = C.c_int(-1)
     window_stats["tried"] += 1
     L.check(lib.sgn_rasterize_window_all(
         n, n_full, len(cands), lo_host, L.ptr(xys_c), L.ptr(_f32c(depths)), L.ptr(_i32c(radii)),
-        L.ptr(_i32c(num_tiles_hit)), L.ptr(conics_c), L.ptr(colors_c), L.ptr(opac_c), int(bool(opacity_is_logit)),
+        L.ptr(_i32c(num_tiles_hit)), L.ptr(conics_c), L.ptr(colors_c), L.ptr(opac_c), int(bool(call.opacity_is_logit)),
         L.ptr(f[0]), L.ptr(f[1]), L.ptr(f[2]), L.ptr(f[3]), L.ptr(f[4]), L.ptr(f[5]), int(num_intersects),
         L.ptr(ids_full), L.ptr(bins_full), qmask, int(img_height), int(img_width), int(block_width), L.ptr(bg_c),
         int(sub), L.ptr(order_ready), L.ptr(out_img), L.ptr(final_Ts), L.ptr(final_idx), L.ptr(ids_out),
         L.ptr(bins_out), L.ptr(order), L.ptr(tile_kmax), L.ptr(rows), rows.numel(), L.ptr(scratch),
         4 * scratch.numel() if scratch is not None else 0, L.ptr(arena), arena.numel(), pinned.data_ptr(),
-        C.byref(matched), ro_ptr, stream_ptr), "sgn_rasterize_window_all")
+        C.byref(matched), call.ro_ptr, call.stream_ptr), "sgn_rasterize_window_all")
     if S.pending_checks:
         raise_pending_checks()             # (a host sync has just happened: deferred flags are final)
     if matched.value < 0:
@@ -1611,14 +1648,15 @@ def _forward_window_composite(S, cand, n, xys_c, depths, radii, num_tiles_hit, c
         ids_use, bins_use = ids_full, bins_full
         if order_ready is None and tile_order_enabled:
             _remember_order(S, bins_full, _fwd_long_thresh(ro, block_width), order)
-    return matched.value, n_full, num_intersects, ids_use, bins_use, order_ready if order_ready is not None else order, tile_kmax, rows
+    return (matched.value, None, n_full), (_WINDOW, num_intersects, ids_use, bins_use,
+                                           order_ready if order_ready is not None else order, tile_kmax, rows)
 
 
 # --------------------------------------------------------------- rasterize
 def _remember_depth(S, key, out_depth, final_Ts, final_idx, tile_kmax, first_pass=True):
     """Keep a pass's depth channel and per-pixel state to answer a later depth pass over the same binning.  `first_pass`
     (the plain passes the "auto" policy switched the channel on for): one more accumulated image nobody has asked for
-    yet — after 8 of them the depth passes have stopped coming and "auto" stops accumulating."""
+    yet — with the ninth of them the depth passes have stopped coming and "auto" stops accumulating."""
     S.depth_caches[key] = dict(key=key, D=out_depth, T=final_Ts, idx=final_idx, kmax=tile_kmax)
     while len(S.depth_caches) > _State.BIN_ENTRIES:
         S.depth_caches.popitem(last=False)
@@ -1636,6 +1674,152 @@ def _nothing_visible(img_height, img_width, bg_c, f32):
             torch.zeros(img_height, img_width, **i32), torch.zeros(0, **i32))
 
 
+_DepthPlan = collections.namedtuple("_DepthPlan", "plain reuse proved explicit accumulate cacheable")
+
+
+def _depth_plan(window, ranged, have_points, cull, hit, want_depth, ungrouped, mode, entry_fits, rgb, colors_are_depths,
+                wanted) -> _DepthPlan:
+    """The depth-channel decision of one forward, from plain values: no tensor, no device (fields: DESIGN.md 4.1, stage 3).
+    (round 6: an explicit request on a cached list, with culling off or with an id_range used to get a zero image.)"""
+    plain = not window and not ranged and have_points and cull
+    reuse = plain and hit and not want_depth and ungrouped and mode != "off" and entry_fits and rgb
+    explicit = want_depth and not window and have_points
+    accumulate = not reuse and (explicit or (plain and not hit and wanted))
+    return _DepthPlan(plain, reuse, reuse and colors_are_depths, explicit, accumulate, accumulate and plain and not hit)
+
+
+def _settle_depth(S, plan, route, key, hit, num_intersects, call, tile_kmax) -> None:
+    """The depth channel's bookkeeping after a forward: the table of DESIGN.md 4.1, every difference between the routes
+    kept as it was."""
+    if route is _FRESH:
+        if plan.accumulate and num_intersects >= 1:      # (this route serves plain fresh passes only: cacheable)
+            depth_stats["accumulated"] += 1
+            _remember_depth(S, key, call.out_depth, call.outs[1], call.outs[2], tile_kmax)
+        else:                                            # binned again without the channel: a stale image must not
+            S.depth_caches.pop(key, None)                # answer later.  ALSO when nothing is visible (not so below)
+    elif route is _PLAIN:
+        if plan.reuse:
+            depth_stats["reused"] += 1
+            S.depth_state["unused"] = 0
+        elif plan.accumulate:
+            depth_stats["accumulated"] += 1
+            if plan.cacheable:
+                _remember_depth(S, key, call.out_depth, call.outs[1], call.outs[2], tile_kmax)
+            # else: an explicit request on a cached list / an id range / without culling: not kept — and NOT popped
+            # either, even on a fresh binning (`not hit`); the groups branch pops in that case
+        elif not hit:
+            S.depth_caches.pop(key, None)                # re-binned without the channel: no stale image later
+    elif route is _GROUPS:
+        if plan.accumulate:
+            depth_stats["accumulated"] += 1
+        if plan.cacheable:                               # first_pass=False: a group pass's image does NOT count towards
+            _remember_depth(S, key, call.out_depth, call.outs[1], call.outs[2], tile_kmax, first_pass=False)
+        elif not hit:                                    # the unused images after which "auto" stops accumulating
+            S.depth_caches.pop(key, None)                # (also after an explicit request that is not cacheable)
+    elif route is _PROVEN:
+        depth_stats["reused"] += 1
+        depth_stats["proved_on_host"] += 1
+        S.depth_state["unused"] = 0
+    # _NOTHING (call-by-call, nothing visible): nothing at all, not even the pop the fresh route does in that case
+    # _WINDOW: nothing (a window pass never reuses or accumulates, and its key is not the cached scene's)
+
+
+def _forward_calls(S, call, plan, win, group_split):
+    """The call-by-call route, the reference for the one-call routes' behaviour: binning (cached, a matched window's,
+    prefetched or begun here), rows, then one of four blocks — nothing visible, proven depth reuse, groups, plain."""
+    xys, depths, radii, num_tiles_hit, conics, opacity = call.src
+    n, img_height, img_width, block_width, tile_bounds = call.size
+    xys_c, conics_c, colors_c, opac_c, bg_c = call.dev_in
+    out_img, final_Ts, final_idx = call.outs
+    id_lo, id_hi, window, n_full = call.span
+    lib, dev, key, ro, ro_ptr, stream_ptr = L.load(), call.dev, call.key, call.ro, call.ro_ptr, call.stream_ptr
+    pending, logit, skip_flag, dcache = S.bin_pending, int(bool(call.opacity_is_logit)), call.skip_flag, call.dcache
+    # the per-Gaussian rows are built between the binning's first half and its host sync, so the GPU has work queued
+    # while the host wakes up
+    recs, rows_built = None, 0
+    if n > 0 and not plan.proved:
+        if win is None and not call.hit and pending["key"] != key:
+            _drop_pending()
+            pending["state"] = _bin_prepare_async(n, xys, depths, radii, num_tiles_hit, tile_bounds, block_width, conics,
+                                                  opacity, call.opacity_is_logit, call.cull)
+            pending["key"], pending["keep"] = key, tuple(t.detach() for t in call._t)
+        recs, rows_built = _forward_rows(call, n_full), 1
+        L.check(lib.sgn_raster_build_rows(n_full, L.ptr(xys_c), L.ptr(conics_c), L.ptr(colors_c), L.ptr(opac_c), logit,
+                                          id_lo, id_hi, window, L.ptr(recs), recs.numel(), L.ptr(skip_flag), stream_ptr),
+                "sgn_raster_build_rows")
+    if win is not None:
+        num_intersects, ids, tile_bins = win[1]
+    else:
+        num_intersects, ids, tile_bins = _bin_gaussians_cached(
+            n, xys, depths, radii, num_tiles_hit, tile_bounds, block_width, conics, opacity, call.opacity_is_logit,
+            pre=(key, call._t, call.cull), logit_leaves=call.logit_leaves)
+    ro.ids_qmask = int(bool(getattr(ids, "_sgn_qmask", False)))          # the backward runs with `ro` too
+    if (num_intersects >= 1 and list_window_enabled and (id_hi - id_lo) < list_window_max_frac * n_full
+            and (id_lo, id_hi) != (0, n_full)):
+        # a SMALL window of a shared list (the scene graph's objects-only pass): walk its own entries only
+        ids, tile_bins = _list_window(ids, tile_bins, id_lo, id_hi, ro.ids_qmask)
+        window_stats["sub_lists"] += 1
+    # -- nothing visible: the forward substitutes the background
+    if num_intersects < 1:
+        return _NOTHING, num_intersects, ids, tile_bins, None, None, None
+    if not (rows_built or plan.proved):
+        recs = _forward_rows(call, n_full, num_intersects)
+    # packed forward: the leading tiles of the order whose lists reach adapt_fwd entries get four waves
+    order = _tile_order(tile_bins, None, _fwd_long_thresh(ro, block_width))
+    n_tiles = tile_bins.shape[0]
+    # -- the depth pass, proven on the host: its image comes from the first pass's fourth channel, and its node SHARES that
+    # pass's per-pixel state and tile statistics (same geometry and opacities: same values)
+    if plan.proved:
+        call.outs = (out_img, dcache["T"], dcache["idx"])
+        L.check(lib.sgn_depth_reuse(img_height, img_width, None, L.ptr(dcache["D"]), L.ptr(dcache["T"]),
+                                    L.ptr(dcache["idx"]), L.ptr(bg_c), L.ptr(out_img), None, None, 0, None, None,
+                                    stream_ptr), "sgn_depth_reuse")
+        return _PROVEN, num_intersects, ids, tile_bins, order, dcache["kmax"], None
+    tile_kmax = torch.empty(n_tiles, 2, dtype=torch.int32, device=dev)                       # walk depth, pairs
+    # -- groups: the two group accumulations ride on the main pass (head = ids below the split, tail = the others).  The
+    # smaller group, if small enough, gets its own compacted list: its backward walks that list, so its indices are
+    # recorded in that list's positions; the other one walks the shared list (with the first group's rows inert).
+    if group_split is not None:
+        assert win is None and not call.ranged and block_width == 16
+        split = min(max(int(group_split), 0), n_full)
+        sizes = (split, n_full - split)
+        small = 0 if sizes[0] <= sizes[1] else 1
+        own = small if (list_window_enabled and 0 < sizes[small] < list_window_max_frac * n_full) else -1
+        state = torch.empty(4, img_height, img_width, dtype=torch.float32, device=dev)  # T_head, T_tail, idx_head, idx_tail
+        kmax = torch.empty(2, n_tiles, 2, dtype=torch.int32, device=dev)
+        groups = []
+        for gi, (lo, hi) in enumerate(((0, split), (split, n_full))):
+            g_ids, g_bins = _list_window(ids, tile_bins, lo, hi, ro.ids_qmask) if gi == own else (ids, tile_bins)
+            window_stats["sub_lists"] += int(gi == own)
+            groups.append(dict(lo=lo, hi=hi, own=gi == own, ids=g_ids, bins=g_bins, T=state[gi],
+                               idx=state[2 + gi].view(torch.int32), kmax=kmax[gi]))
+        og = groups[own] if own >= 0 else None
+        L.check(lib.sgn_raster_fwd_groups(
+            img_height, img_width, n_full, num_intersects, L.ptr(ids), L.ptr(tile_bins),
+            L.ptr(xys_c), L.ptr(conics_c), L.ptr(colors_c), L.ptr(opac_c), logit, L.ptr(bg_c),
+            L.ptr(out_img), L.ptr(final_Ts), L.ptr(final_idx), L.ptr(recs), recs.numel(), rows_built, L.ptr(order),
+            L.ptr(tile_kmax), L.ptr(call.depths_c), L.ptr(call.out_depth), split, own,
+            L.ptr(og["ids"]) if og else None, L.ptr(og["bins"]) if og else None, L.ptr(state), L.ptr(kmax),
+            ro_ptr, stream_ptr), "sgn_raster_fwd_groups")
+        group_stats["passes"] += 1
+        call.groups = groups
+        return _GROUPS, num_intersects, ids, tile_bins, order, tile_kmax, recs
+    # -- plain; with `plan.reuse` queued behind the flag that turns it into a no-op where the colours are the depths
+    L.check(lib.sgn_raster_fwd(
+        img_height, img_width, block_width, n_full, num_intersects, L.ptr(ids), L.ptr(tile_bins),
+        L.ptr(xys_c), L.ptr(conics_c), L.ptr(colors_c), L.ptr(opac_c), logit, id_lo, id_hi,
+        window, L.ptr(bg_c), L.ptr(out_img), L.ptr(final_Ts), L.ptr(final_idx), L.ptr(recs), recs.numel(),
+        rows_built, L.ptr(order), L.ptr(tile_kmax), L.ptr(call.depths_c), L.ptr(call.out_depth), L.ptr(skip_flag),
+        ro_ptr, stream_ptr), "sgn_raster_fwd")
+    if plan.reuse:
+        L.check(lib.sgn_depth_reuse(img_height, img_width, L.ptr(skip_flag), L.ptr(dcache["D"]),
+                                    L.ptr(dcache["T"]), L.ptr(dcache["idx"]), L.ptr(bg_c), L.ptr(out_img),
+                                    L.ptr(final_Ts), L.ptr(final_idx), tile_kmax.numel(),
+                                    L.ptr(dcache["kmax"]), L.ptr(tile_kmax), stream_ptr), "sgn_depth_reuse")
+        recs = None                        # the rows were not built if the flag said "reuse": the backward packs them
+    return _PLAIN, num_intersects, ids, tile_bins, order, tile_kmax, recs
+
+
 class _RasterizeGaussians(Function):
     @staticmethod
     def forward(ctx, xys, depths, radii, conics, num_tiles_hit, colors, opacity, img_height, img_width,
@@ -1651,35 +1835,15 @@ class _RasterizeGaussians(Function):
                                          (opacity if not opacity_logits else None))
         ctx.alpha_clamp_bwd = semantics().alpha_clamp_bwd      # the backward runs with the CALL's value
         ctx.set_materialize_grads(False)       # an unused alpha / depth output arrives as None, not as a zero image
-        dev = L.require_device(xys, depths, radii, conics, num_tiles_hit, colors, opacity, background)
-        num_points = xys.size(0)
-        tile_bounds = ((img_width + block_width - 1) // block_width,
-                       (img_height + block_width - 1) // block_width, 1)
-        if colors.shape[-1] != 3:
-            raise NotImplementedError(
-                "only the 3-channel rasterize path is implemented (the reference never uses N-D colours: "
-                "sgn_splatfacto.py:988 repeats depth x3 to stay on it)")
-        xys_c, conics_c, colors_c = _f32c(xys), _f32c(conics), _f32c(colors)
-        opac_c, bg_c = _f32c(opacity).reshape(-1), _f32c(background)
-        f32 = dict(dtype=torch.float32, device=dev)
-        lib = L.load()
-        ro = L.opts().copy()              # this call's kernel options: the backward runs with the same ones
-        ro_ptr = C.byref(ro)
-        # everything that does not depend on the intersection count is prepared BEFORE the binning's host sync: the
-        # GPU idles from the moment the count is known until the next launch arrives, so that window is kept short
-        out_img = torch.empty(img_height, img_width, 3, **f32)
-        final_Ts = torch.empty(img_height, img_width, **f32)
-        final_idx = torch.empty(img_height, img_width, dtype=torch.int32, device=dev)
-        stream_ptr = L.stream_ptr()
-        key, _t, cull = _cache_key(xys, depths, radii, num_tiles_hit, tile_bounds, block_width, conics, opacity,
-                                   opacity_is_logit)
+        # 1. the per-call record: contiguous inputs, options, outputs, binning key (all before any host sync)
+        call = _RasterCall(xys, depths, radii, conics, num_tiles_hit, colors, opacity, img_height, img_width, block_width,
+                           background, opacity_is_logit, opacity_logits)
+        num_points, key, _t, cull, dev = xys.size(0), call.key, call._t, call.cull, call.dev
         S = _S()
-        _bin_pending, _depth_state = S.bin_pending, S.depth_state
-        hit = binning_cache_enabled and S.has_binning(key)
-        # a sub-model's copy of a window of the cached scene?  (drop-in scene-graph path; see _match_window)
-        n_full, window, win = num_points, 0, None
-        wcomp = None
-        if id_range is None and not hit and _bin_pending["key"] != key and not want_depth:
+        hit = call.hit = binning_cache_enabled and S.has_binning(key)
+        # 2. a sub-model's copy of a window of the cached scene?  (drop-in scene-graph path; see _match_window)
+        win = res = None
+        if id_range is None and not hit and S.bin_pending["key"] != key and not want_depth:
             # (an explicit depth request is never served as a window of another scene: the window's tensors are
             # window-local, the channel's depths would be read at full-scene ids — it is binned as a scene of its own)
             cand = None
@@ -1688,186 +1852,61 @@ class _RasterizeGaussians(Function):
                     and num_tiles_hit.dtype is torch.int32):
                 cand = _window_candidate(S, key[len(_t):], num_points, _t)
             if cand is not None:
-                # ONE library call: comparison on the device, verdict, rows, sub-list, order, forward (round 6)
-                wcomp = _forward_window_composite(S, cand, num_points, xys_c, depths, radii, num_tiles_hit, conics_c,
-                                                  colors_c, opac_c, opacity_is_logit, cull, img_height, img_width,
-                                                  block_width, bg_c, out_img, final_Ts, final_idx, ro, ro_ptr, stream_ptr)
+                # the one-call window route recognises and runs in ONE library call (round 6)
+                win, res = _forward_window_composite(S, call, cand) or (None, None)
             else:
                 win = _match_window(key[len(_t):], num_points, xys, depths, radii, num_tiles_hit, conics, opacity, cull,
                                     opacity_logits)
-        if wcomp is not None:
-            lo, n_full, num_intersects, gaussian_ids_sorted, tile_bins, order, tile_kmax, recs = wcomp
-            id_lo, id_hi, window = lo, lo + num_points, 1
-            win = (lo, None, n_full)                      # (a window pass for everything below: sink, ctx)
-        elif win is not None:
-            lo, cached, n_full = win
-            id_lo, id_hi, window = lo, lo + num_points, 1
-        else:
-            id_lo, id_hi = (0, num_points) if id_range is None else (int(id_range[0]), int(id_range[1]))
-        # depth channel: is this the reference's depth pass over the geometry of the pass before it (answer it from that
-        # pass's fourth channel), or a first pass that should accumulate the channel?
-        plain = win is None and id_range is None and num_points > 0 and cull
-        dcache = S.depth_caches.get(key)
-        reuse = (plain and hit and not want_depth and group_split is None and depth_channel != "off" and dcache is not None
-                 and colors_c.shape == (num_points, 3) and dcache["D"].shape == (img_height, img_width))
+        call.ranged = id_range is not None
+        if win is not None:                # (lo, the cached binning — None once the one-call route has run —, n_full)
+            call.span = (win[0], win[0] + num_points, 1, win[2])
+        elif id_range is not None:
+            call.span = (int(id_range[0]), int(id_range[1]), 0, num_points)
+        # 3. depth channel: the reference's depth pass over the last pass's geometry, or a pass that should accumulate?
+        dcache = call.dcache = S.depth_caches.get(key)
+        colors_c = call.dev_in[2]
+        plan = _depth_plan(win is not None, id_range is not None, num_points > 0, cull, hit, bool(want_depth),
+                           group_split is None, depth_channel,
+                           dcache is not None and dcache["D"].shape == (img_height, img_width),
+                           colors_c.shape == (num_points, 3), bool(colors_are_depths), _depth_wanted(S))
+        plain, reuse, proved, _explicit, accumulate, _cacheable = plan
         if plain and hit and not reuse and depth_channel == "auto" and not want_depth:
-            _depth_state["want"] = True        # a second pass over the same geometry: accumulate from the next step on
-        # `want_depth` (the fused API's depth_channel=True) is an explicit request: the channel is accumulated whatever the
-        # binning's history — a cached list, culling switched off, an id_range pass (round 6: such calls used to get a zero
-        # image; a call that asks for depth is not matched as a window of another scene, see above).  The
-        # "auto" policy of the drop-in surface accumulates on a plain, freshly binned pass only, and only such a pass's
-        # image may answer a later depth pass (`depth_cacheable`).
-        explicit = bool(want_depth) and win is None and num_points > 0
-        accumulate = (not reuse) and (explicit or (plain and not hit and _depth_wanted()))
-        depth_cacheable = accumulate and plain and not hit
-        depths_c = _f32c(depths) if (reuse or accumulate) else None
-        skip_flag = None
-        proved = bool(reuse and colors_are_depths)      # the host knows: no flag, no conditional launches, no copies
-        if reuse and not proved:
-            skip_flag = torch.empty(1, dtype=torch.int32, device=dev)
-            L.check(lib.sgn_colors_match_depths(num_points, L.ptr(colors_c), L.ptr(depths_c), L.ptr(skip_flag),
-                                                stream_ptr), "sgn_colors_match_depths")
-        out_depth = torch.empty(img_height, img_width, **f32) if accumulate else None
-        # ONE library call for the whole node where nothing special is asked (sgn_rasterize_fwd_all, round 5): the full scene,
-        # a fresh binning, no depth channel / reuse / groups, a capacity known from earlier calls
-        comp = None
-        if (wcomp is None and composite_forward and tile_order_enabled and plain and not hit and not reuse
-                and group_split is None and _bin_pending["key"] != key and not S.pending_checks):
+            S.depth_state["want"] = True   # a second pass over the same geometry: accumulate from the next step on
+        if reuse or accumulate:
+            depths_c = _f32c(depths)
+            if reuse and not proved:       # the device-side comparison whose flag turns the queued forward into a no-op
+                call.skip_flag = torch.empty(1, dtype=torch.int32, device=dev)
+                L.check(L.load().sgn_colors_match_depths(num_points, L.ptr(colors_c), L.ptr(depths_c),
+                                                         L.ptr(call.skip_flag), call.stream_ptr), "sgn_colors_match_depths")
+            if accumulate:
+                call.depths_c, call.out_depth = depths_c, torch.empty(img_height, img_width, dtype=torch.float32, device=dev)
+        # 4. one route: ONE library call for the whole node where nothing special is asked (round 5), else call by call
+        if (res is None and composite_forward and tile_order_enabled and plain and not hit and not reuse
+                and group_split is None and S.bin_pending["key"] != key and not S.pending_checks):
             _drop_pending()        # a prefetched binning of OTHER tensors will never be finished
-            comp = _forward_composite(S, key, _t, cull, num_points, xys_c, depths, radii, conics_c, colors_c, opac_c,
-                                      opacity_is_logit, img_height, img_width, block_width, tile_bounds, bg_c, out_img,
-                                      final_Ts, final_idx, ro, ro_ptr, opacity_logits, stream_ptr,
-                                      out_depth if accumulate else None)
-        if wcomp is not None:
-            pass                               # everything was queued by the one call above
-        elif comp is not None:
-            num_intersects, gaussian_ids_sorted, tile_bins, order, tile_kmax, recs = comp
-            if num_intersects < 1:
-                recs = None
-                out_depth = None               # never written (no forward ran): the want_depth branch below returns zeros
-                out_img, final_Ts, final_idx, gaussian_ids_sorted = _nothing_visible(img_height, img_width, bg_c, f32)
-            if accumulate and num_intersects >= 1:      # (the composite serves plain fresh passes only: cacheable)
-                depth_stats["accumulated"] += 1
-                _remember_depth(S, key, out_depth, final_Ts, final_idx, tile_kmax)
-            else:
-                S.depth_caches.pop(key, None)  # binned again without the channel: a stale image must not answer later
-        else:
-            # ... and the per-Gaussian rows are built between the binning's first half and its host sync, so the GPU has
-            # work queued while the host wakes up
-            recs, rows_built = None, 0
-            if num_points > 0 and not proved:
-                if win is None and not hit and _bin_pending["key"] != key:
-                    _drop_pending()
-                    _bin_pending["state"] = _bin_prepare_async(num_points, xys, depths, radii, num_tiles_hit, tile_bounds,
-                                                               block_width, conics, opacity, opacity_is_logit, cull)
-                    _bin_pending["key"], _bin_pending["keep"] = key, tuple(t.detach() for t in _t)
-                recs = L.workspace(lib.sgn_raster_workspace_bytes(n_full, 0, ro_ptr), dev)
-                L.check(lib.sgn_raster_build_rows(n_full, L.ptr(xys_c), L.ptr(conics_c), L.ptr(colors_c), L.ptr(opac_c),
-                                                  int(bool(opacity_is_logit)), id_lo, id_hi, window, L.ptr(recs),
-                                                  recs.numel(), L.ptr(skip_flag), stream_ptr), "sgn_raster_build_rows")
-                rows_built = 1
-            if win is not None:
-                num_intersects, gaussian_ids_sorted, tile_bins = cached
-            else:
-                num_intersects, gaussian_ids_sorted, tile_bins = _bin_gaussians_cached(
-                    num_points, xys, depths, radii, num_tiles_hit, tile_bounds, block_width, conics, opacity,
-                    opacity_is_logit, pre=(key, _t, cull), logit_leaves=opacity_logits)
-            ro.ids_qmask = int(bool(getattr(gaussian_ids_sorted, "_sgn_qmask", False)))   # the backward runs with `ro` too
-            if (num_intersects >= 1 and list_window_enabled and (id_hi - id_lo) < list_window_max_frac * n_full
-                    and (id_lo, id_hi) != (0, n_full)):
-                # a SMALL window of a shared list (the scene graph's objects-only pass): walk its own entries only
-                gaussian_ids_sorted, tile_bins = _list_window(gaussian_ids_sorted, tile_bins, id_lo, id_hi, ro.ids_qmask)
-                window_stats["sub_lists"] += 1
-            if proved and num_intersects >= 1:
-                # the depth pass, proven on the host: its image comes from the first pass's fourth channel, and its node
-                # SHARES that pass's per-pixel state and tile statistics (same geometry and opacities: same values)
-                final_Ts, final_idx, tile_kmax = dcache["T"], dcache["idx"], dcache["kmax"]
-                order = _tile_order(tile_bins, None, _fwd_long_thresh(ro, block_width))
-                L.check(lib.sgn_depth_reuse(img_height, img_width, None, L.ptr(dcache["D"]), L.ptr(final_Ts),
-                                            L.ptr(final_idx), L.ptr(bg_c), L.ptr(out_img), None, None, 0, None, None,
-                                            stream_ptr), "sgn_depth_reuse")
-                depth_stats["reused"] += 1
-                depth_stats["proved_on_host"] += 1
-                _depth_state["unused"] = 0
-            elif num_intersects < 1:
-                recs = None
-                out_depth = None            # never written (no forward ran): the want_depth branch below returns zeros
-                out_img, final_Ts, final_idx, gaussian_ids_sorted = _nothing_visible(img_height, img_width, bg_c, f32)
-                tile_bins = torch.zeros(tile_bounds[0] * tile_bounds[1], 2, dtype=torch.int32, device=dev)
-            elif group_split is not None:
-                # the main pass with the two group accumulations riding on it (sgn_raster_fwd_groups): head = ids below the
-                # split, tail = the others.  The smaller group, if small enough, gets its own compacted list: its backward
-                # walks that list, so its indices are recorded in that list's positions (and its forward walk finishes
-                # there); the other one walks the shared list (with the first group's rows inert).
-                assert win is None and id_range is None and block_width == 16
-                if not rows_built:
-                    recs = L.workspace(lib.sgn_raster_workspace_bytes(n_full, num_intersects, ro_ptr), dev)
-                order = _tile_order(tile_bins, None, _fwd_long_thresh(ro, block_width))
-                n_tiles = tile_bins.shape[0]
-                tile_kmax = torch.empty(n_tiles, 2, dtype=torch.int32, device=dev)
-                split = min(max(int(group_split), 0), n_full)
-                sizes = (split, n_full - split)
-                small = 0 if sizes[0] <= sizes[1] else 1
-                own = small if (list_window_enabled and 0 < sizes[small] < list_window_max_frac * n_full) else -1
-                state = torch.empty(4, img_height, img_width, **f32)          # T_head, T_tail, idx_head, idx_tail
-                kmax = torch.empty(2, n_tiles, 2, dtype=torch.int32, device=dev)
-                groups = []
-                for gi, (lo, hi) in enumerate(((0, split), (split, n_full))):
-                    g_ids, g_bins = (_list_window(gaussian_ids_sorted, tile_bins, lo, hi, ro.ids_qmask) if gi == own
-                                     else (gaussian_ids_sorted, tile_bins))
-                    window_stats["sub_lists"] += int(gi == own)
-                    groups.append(dict(lo=lo, hi=hi, own=gi == own, ids=g_ids, bins=g_bins, T=state[gi],
-                                       idx=state[2 + gi].view(torch.int32), kmax=kmax[gi]))
-                og = groups[own] if own >= 0 else None
-                L.check(lib.sgn_raster_fwd_groups(
-                    img_height, img_width, n_full, num_intersects, L.ptr(gaussian_ids_sorted), L.ptr(tile_bins),
-                    L.ptr(xys_c), L.ptr(conics_c), L.ptr(colors_c), L.ptr(opac_c), int(bool(opacity_is_logit)), L.ptr(bg_c),
-                    L.ptr(out_img), L.ptr(final_Ts), L.ptr(final_idx), L.ptr(recs), recs.numel(), rows_built, L.ptr(order),
-                    L.ptr(tile_kmax), L.ptr(depths_c) if accumulate else None, L.ptr(out_depth), split, own,
-                    L.ptr(og["ids"]) if og else None, L.ptr(og["bins"]) if og else None, L.ptr(state), L.ptr(kmax),
-                    ro_ptr, stream_ptr), "sgn_raster_fwd_groups")
-                group_stats["passes"] += 1
-                ctx.groups = groups
-                if accumulate:
-                    depth_stats["accumulated"] += 1
-                if depth_cacheable:
-                    _remember_depth(S, key, out_depth, final_Ts, final_idx, tile_kmax, first_pass=False)
-                elif not hit:
-                    S.depth_caches.pop(key, None)
-            else:
-                if not rows_built:
-                    recs = L.workspace(lib.sgn_raster_workspace_bytes(n_full, num_intersects, ro_ptr), dev)
-                # packed forward: the leading tiles of the order whose lists reach adapt_fwd entries get four waves
-                order = _tile_order(tile_bins, None, _fwd_long_thresh(ro, block_width))
-                tile_kmax = torch.empty(tile_bins.shape[0], 2, dtype=torch.int32, device=dev)   # walk depth, pairs
-                L.check(lib.sgn_raster_fwd(
-                    img_height, img_width, block_width, n_full, num_intersects, L.ptr(gaussian_ids_sorted), L.ptr(tile_bins),
-                    L.ptr(xys_c), L.ptr(conics_c), L.ptr(colors_c), L.ptr(opac_c), int(bool(opacity_is_logit)), id_lo, id_hi,
-                    window, L.ptr(bg_c), L.ptr(out_img), L.ptr(final_Ts), L.ptr(final_idx), L.ptr(recs), recs.numel(),
-                    rows_built, L.ptr(order), L.ptr(tile_kmax), L.ptr(depths_c) if accumulate else None,
-                    L.ptr(out_depth), L.ptr(skip_flag), ro_ptr, stream_ptr), "sgn_raster_fwd")
-                if reuse:
-                    L.check(lib.sgn_depth_reuse(img_height, img_width, L.ptr(skip_flag), L.ptr(dcache["D"]),
-                                                L.ptr(dcache["T"]), L.ptr(dcache["idx"]), L.ptr(bg_c), L.ptr(out_img),
-                                                L.ptr(final_Ts), L.ptr(final_idx), tile_kmax.numel(),
-                                                L.ptr(dcache["kmax"]), L.ptr(tile_kmax), stream_ptr), "sgn_depth_reuse")
-                    recs = None                    # the rows were not built if the flag said "reuse": the backward packs them
-                    depth_stats["reused"] += 1
-                    _depth_state["unused"] = 0
-                elif accumulate and not depth_cacheable:
-                    depth_stats["accumulated"] += 1            # an explicit request on a cached list / an id range: not kept
-                elif accumulate:
-                    depth_stats["accumulated"] += 1
-                    _remember_depth(S, key, out_depth, final_Ts, final_idx, tile_kmax)
-                elif not hit:
-                    S.depth_caches.pop(key, None)  # re-binned without the channel: a stale image must not answer later
-        # (the sink hears of passes that WILL have a backward only: a forward under no_grad — an evaluation image between
-        # two training steps — announces nothing; such an announcement used to stay behind and count as a second view of
-        # the next step whenever its list happened to land on another address)
+            res = _forward_composite(S, call)
+        if res is None:
+            res = _forward_calls(S, call, plan, win, group_split)
+        route, num_intersects, gaussian_ids_sorted, tile_bins, _order, tile_kmax, recs = res
+        f32 = dict(dtype=torch.float32, device=dev)
+        # 5. nothing visible: the background everywhere, no rows, no channel.  (Every route comes through here where the
+        # one-call window route used to be exempt: a window's cached list has at least one entry, `_window_candidate`.)
+        if num_intersects < 1:
+            recs = None
+            call.out_depth = None          # never written (no forward ran): the want_depth branch below returns zeros
+            *call.outs, gaussian_ids_sorted = _nothing_visible(img_height, img_width, call.dev_in[4], f32)
+            if route is _NOTHING:          # (the fresh route keeps the bins its emission cleared)
+                tile_bins = torch.zeros(call.size[4][0] * call.size[4][1], 2, dtype=torch.int32, device=dev)
+        # 6. the depth channel's bookkeeping
+        _settle_depth(S, plan, route, key, hit, num_intersects, call, tile_kmax)
+        # 7. (the sink hears of passes that WILL have a backward only: a forward under no_grad — an evaluation image
+        # between two training steps — announces nothing; such an announcement used to stay behind and count as a second
+        # view of the next step whenever its list happened to land on another address)
         sink = _touch_sink if (getattr(_call_state, "grad", True) and any(ctx.needs_input_grad)) else None
+        id_lo, id_hi, window, n_full = call.span
         if sink is not None and num_intersects >= 1 and win is None and id_range is None and not proved:
             # data-parallel row exchange: which Gaussians this view's backward can touch (the walked entries)
-            sink.after_forward(gaussian_ids_sorted, tile_bins, tile_kmax, n_full, ro.ids_qmask)
+            sink.after_forward(gaussian_ids_sorted, tile_bins, tile_kmax, n_full, call.ro.ids_qmask)
         if sink is not None and num_intersects >= 1 and (win is not None or id_range is not None
                                                            or group_split is not None):
             # a sub-model pass / group accumulation walks entries the full pass's list of walked rows does not cover
@@ -1875,22 +1914,27 @@ class _RasterizeGaussians(Function):
             extra = getattr(sink, "extra_pass", None)
             if extra is not None:
                 extra()
+        # 8. what the backward needs
+        (out_img, final_Ts, final_idx), out_depth = call.outs, call.out_depth
         ctx.img_width, ctx.img_height, ctx.block_width = img_width, img_height, block_width
         ctx.num_intersects = num_intersects
         ctx.opacity_is_logit = int(bool(opacity_is_logit))
         ctx.id_range = (id_lo, id_hi)
-        ctx.window, ctx.n_full, ctx.ro = window, n_full, ro
+        ctx.window, ctx.n_full, ctx.ro = window, n_full, call.ro
         ctx.tile_kmax = tile_kmax if num_intersects >= 1 else None
         ctx.opacity_shape = opacity.shape
         ctx.recs = recs
-        ctx.save_for_backward(gaussian_ids_sorted, tile_bins, xys_c, conics_c, colors_c, opac_c, bg_c,
-                              final_Ts, final_idx, *([_f32c(colors_pre)] if colors_pre is not None else []))
+        if call.groups is not None:
+            ctx.groups = call.groups
+        ctx.save_for_backward(gaussian_ids_sorted, tile_bins, *call.dev_in, final_Ts, final_idx,
+                              *([_f32c(colors_pre)] if colors_pre is not None else []))
+        # 9. the return value's shape
         if group_split is not None:
             if want_depth and out_depth is None:
                 out_depth = torch.zeros(img_height, img_width, **f32)
             if out_depth is not None:
                 ctx.mark_non_differentiable(out_depth)
-            gs = getattr(ctx, "groups", None)
+            gs = call.groups
             accs = [(1 - g["T"]) if gs is not None else torch.zeros(img_height, img_width, **f32)
                     for g in (gs or (None, None))]
             return out_img, 1 - final_Ts, out_depth, accs[0], accs[1]
@@ -1898,11 +1942,9 @@ class _RasterizeGaussians(Function):
             if out_depth is None:                 # nothing visible / a path without the channel: the two-pass image
                 out_depth = torch.zeros(img_height, img_width, **f32)
             ctx.mark_non_differentiable(out_depth)
-            out_alpha = 1 - final_Ts
-            return out_img, out_alpha, out_depth
+            return out_img, 1 - final_Ts, out_depth
         if return_alpha:
-            out_alpha = 1 - final_Ts
-            return out_img, out_alpha
+            return out_img, 1 - final_Ts
         return out_img
 
     @staticmethod
@@ -1956,14 +1998,16 @@ class _RasterizeGaussians(Function):
             # (a group walk's statistics hold the walk depth only — sgn_raster_fwd_groups records no per-tile pair count
             # for the head / tail groups — so the small-splat classification, which reads that count, stays off for it)
             pairs_known = kmax is ctx.tile_kmax
+            S, n_tiles = _S(), bins.shape[0]
+            if composite_backward:
+                order = torch.empty(n_tiles + 2, dtype=torch.int32, device=dev) if tile_order_enabled else None
+            else:
+                order = _tile_order(bins, kmax, ctx.ro.adapt_bwd, pairs_known=pairs_known)
+            if order is not None and not window and id_range == (0, n):
+                S.walk_stat = order[-1:]             # rides to the host with the next binning's count (mask policy)
             if composite_backward:
                 # ONE library call: launch order + reverse walks + unpack (sgn_rasterize_bwd_all, round 6)
-                S = _S()
-                n_tiles = bins.shape[0]
-                order = torch.empty(n_tiles + 2, dtype=torch.int32, device=dev) if tile_order_enabled else None
                 scratch = _order_scratch(S, lib, n_tiles, dev) if order is not None else None
-                if order is not None and not window and id_range == (0, n):
-                    S.walk_stat = order[-1:]         # rides to the host with the next binning's count (mask policy)
                 first, last = (1, 1) if part is None else (int(part[0]), int(part[1]))
                 L.check(lib.sgn_rasterize_bwd_all(
                     H, W, ctx.block_width, ctx.n_full, ctx.num_intersects, L.ptr(ids), L.ptr(bins), L.ptr(kmax),
@@ -1977,9 +2021,6 @@ class _RasterizeGaussians(Function):
                     "sgn_rasterize_bwd_all")
                 composite_stats["backwards"] += 1
                 return out
-            order = _tile_order(bins, kmax, ctx.ro.adapt_bwd, pairs_known=pairs_known)
-            if order is not None and not window and id_range == (0, n):
-                _S().walk_stat = order[-1:]          # rides to the host with the next binning's count (mask policy)
             args = (H, W, ctx.block_width, ctx.n_full, ctx.num_intersects, L.ptr(ids), L.ptr(bins),
                     L.ptr(xys), L.ptr(conics), L.ptr(colors), L.ptr(opacity),
                     logit_mode, id_range[0],

@@ -15,16 +15,43 @@ HEADER = os.path.join(ROOT, "include", "sgn_rast.h")
 PKG = os.path.join(ROOT, "street-gaussians-ns_amd")
 
 
-def _header_functions():
+_PROTOTYPE = re.compile(r"\b((?:int|size_t|void|double|const char \*)\s*\*?)\s*(sgn_\w+)\s*\(([^;{]*)\)\s*;")
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
+            "double": ctypes.c_double, "size_t": ctypes.c_size_t}
+
+
+def _prototypes():
+    """name -> (return type text, [parameter type text]) of every entry point, comments and parameter names stripped."""
     src = open(HEADER).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     src = re.sub(r"//[^\n]*", "", src)
     out = {}
-    for m in re.finditer(r"\b(?:int|size_t|void|double|const char \*)\s*\*?\s*(sgn_\w+)\s*\(([^;{]*)\)\s*;", src):
-        name, args = m.group(1), m.group(2).strip()
-        n = 0 if args in ("", "void") else len([a for a in args.split(",") if a.strip()])
-        out[name] = n
+    for m in _PROTOTYPE.finditer(src):
+        args = m.group(3).strip()
+        params = [] if args in ("", "void") else [" ".join(a.split()) for a in args.split(",") if a.strip()]
+        # `const float *xys` -> `const float *`, `int n` -> `int`, `float bg[3]` -> `float []`
+        params = [re.sub(r"\b\w+\s*(\[\w*\])?$", lambda t: "[]" if t.group(1) else "", a).strip() for a in params]
+        out[m.group(2)] = (" ".join(m.group(1).split()), params)
     return out
+
+
+def _header_functions():
+    return {name: len(params) for name, (_, params) in _prototypes().items()}
+
+
+def _is_address(ctype) -> bool:
+    return ctype is ctypes.c_void_p or (isinstance(ctype, type) and issubclass(ctype, ctypes._Pointer))
+
+
+def _class_matches(text: str, ctype) -> bool:
+    """Does a ctypes class carry a C parameter / return type written as `text`?"""
+    if text == "void":
+        return ctype is None
+    if text == "const char *":
+        return ctype is ctypes.c_char_p
+    if "*" in text or "[" in text or text == "sgn_stream_t":
+        return _is_address(ctype)
+    return text in _SCALARS and ctype is _SCALARS[text]
 
 
 @pytest.fixture(scope="module")
@@ -56,6 +83,12 @@ def test_ctypes_table_matches_header(built_lib):
     assert set(fns) == set(built_lib.SIGNATURES), set(fns) ^ set(built_lib.SIGNATURES)
     for name, nargs in fns.items():
         assert len(built_lib.SIGNATURES[name][1]) == nargs, name
+    # ... and argument by argument, by class: an address for every pointer / array / stream, the scalar's own width else
+    for name, (ret, params) in _prototypes().items():
+        res, args = built_lib.SIGNATURES[name]
+        assert _class_matches(ret, res), (name, "returns", ret, res)
+        for i, (text, ctype) in enumerate(zip(params, args)):
+            assert _class_matches(text, ctype), (name, i, text, ctype)
     built_lib.load()  # sets restype/argtypes on every symbol
 
 
