@@ -1116,6 +1116,24 @@ int sgn_depth_metrics(int img_h, int img_w, const float *dsum, const float *alph
                       const unsigned char *mask /*may be NULL*/, float *out5, void *ws, size_t ws_bytes,
                       sgn_stream_t stream);
 
+/* ANTIALIASED OPACITY (rasterize_mode "antialiased", sgn_splatfacto.py:214-222, :947: the multiply the reference leaves
+ * commented out).  The effective opacity of row i from its logit l and the projection's compensation factor c
+ * (sqrt(max(0, det / det_blurred)); 0 on a culled row), fp32, no contraction:
+ *   s   = 1.f / (1.f + expf(-l))              the sigmoid as the rasterizer's row build spells it
+ *   o   = s * c
+ *   v_l = ((v_o * c) * s) * (1.f - s)         left to right, as the rasterizer's gradient unpack chains its sigmoid
+ *   v_c = v_o * s
+ * so a culled row has o = 0 and v_l = 0, and with c == 1.0f o has exactly the bits the fused rasterizer forms from the
+ * logit itself.  `opacities` is handed on as PROBABILITIES (opacity_is_logit = 0) to every raster / binning entry; v_o is
+ * the sum of those passes' opacity gradients, v_c goes to the projection backward as v_compensation.
+ * One row per lane, 4-byte accesses: the arrays need no more than float alignment.  v_opacity_logits / v_compensation:
+ * either may be NULL (not wanted); both NULL returns 0 without a launch, as n == 0 does.
+ * Return codes: -1 n < 0; -2 a required pointer is NULL. */
+int sgn_aa_opacity_fwd(int n, const float *opacity_logits, const float *compensation, float *opacities,
+                       sgn_stream_t stream);
+int sgn_aa_opacity_bwd(int n, const float *opacity_logits, const float *compensation, const float *v_opacities,
+                       float *v_opacity_logits, float *v_compensation, sgn_stream_t stream);
+
 /* BATCHED VIEWS (no upstream counterpart; gsplat 1.x takes [C] cameras per call).  B = n_views cameras share one image
  * size (img_h, img_w), 16x16 tiles and one set of N Gaussians in the fused front end's raw form (means, log-scales, raw
  * quaternions, opacity logits, features_dc [N,1,3], features_rest [N,k-1,3]; no scene graph).  Row b*N + i of every

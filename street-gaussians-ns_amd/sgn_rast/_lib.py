@@ -161,6 +161,8 @@ SIGNATURES = {
     "sgn_depth_loss_fwd": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "sgn_depth_loss_bwd": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "sgn_depth_metrics": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sgn_aa_opacity_fwd": (_i, [_i, _vp, _vp, _vp, _vp]),
+    "sgn_aa_opacity_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

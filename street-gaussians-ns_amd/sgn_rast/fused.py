@@ -400,11 +400,60 @@ def spherical_harmonics_fused(degrees_to_use: int, means, cam_pos, features_dc, 
                           post_half_clamp, claimed)
 
 
+class _AntialiasedOpacities(Function):
+    @staticmethod
+    def forward(ctx, opacity_logits, compensation):
+        dev = L.require_device(opacity_logits, compensation)
+        n = compensation.shape[0]
+        if compensation.dim() != 1 or opacity_logits.numel() != n or opacity_logits.dim() not in (1, 2):
+            raise ValueError(f"opacity_logits [N] or [N,1] and compensation [N] expected, got "
+                             f"{tuple(opacity_logits.shape)} and {tuple(compensation.shape)}")
+        logits_c, comp_c = _f32c(opacity_logits).reshape(-1), _f32c(compensation)
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        L.check(L.load().sgn_aa_opacity_fwd(n, L.ptr(logits_c), L.ptr(comp_c), L.ptr(out), L.stream_ptr()),
+                "sgn_aa_opacity_fwd")
+        ctx.logits_shape = opacity_logits.shape
+        ctx.arena_leaves = _ops._arena_leaves(opacity_logits)
+        ctx.save_for_backward(logits_c, comp_c)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, v_opac):
+        want_l, want_c = ctx.needs_input_grad
+        if v_opac is None or not (want_l or want_c):
+            return None, None
+        logits, comp = ctx.saved_tensors
+        n, f32 = comp.shape[0], dict(dtype=torch.float32, device=comp.device)
+        v_l = _ops._leaf_grad(getattr(ctx, "arena_leaves", None), 0, (n,), f32) if want_l else None
+        v_c = torch.empty(n, **f32) if want_c else None
+        L.check(L.load().sgn_aa_opacity_bwd(n, L.ptr(logits), L.ptr(comp), L.ptr(_f32c(v_opac)), L.ptr(v_l), L.ptr(v_c),
+                                            L.stream_ptr()), "sgn_aa_opacity_bwd")
+        return (None if v_l is None else v_l.view(ctx.logits_shape)), v_c
+
+
+def antialiased_opacities(opacity_logits: torch.Tensor, compensation: torch.Tensor) -> torch.Tensor:
+    """``torch.sigmoid(opacity_logits) * compensation`` -> [N]: the effective opacity of the antialiased rasterize mode
+    (the multiply the reference leaves commented out, ``sgn_splatfacto.py:947``) in one kernel, forward and backward
+    (``csrc/antialias.hip``; the fp32 contract is in ``include/sgn_rast.h``).  ``opacity_logits`` [N] or [N,1],
+    ``compensation`` [N] as the projection returns it (0 on a culled row).  The result holds PROBABILITIES: hand it to
+    :func:`rasterize_gaussians_fused` as ``compensation=`` does, or to any entry that takes ``opacity_is_logit=False``
+    — and hand every pass of one render the SAME tensor: the binning cache keeps hitting and autograd sums the passes'
+    gradients before this node's backward splits them into the logits' and the factor's (the latter reaches the
+    covariance through the projection's ``v_compensation``).  Only the gradients that are needed are computed."""
+    return _AntialiasedOpacities.apply(opacity_logits.contiguous(), compensation.contiguous())
+
+
 def rasterize_gaussians_fused(xys, depths, radii, conics, num_tiles_hit, colors, opacity_logits, img_height,
                               img_width, block_width, background=None, return_alpha=False, id_range=None,
-                              depth_channel=False, group_split=None):
+                              depth_channel=False, group_split=None, compensation=None, opacity_is_logit=True):
     """``rasterize_gaussians(..., torch.sigmoid(opacity_logits), ...)`` with the sigmoid (and its backward)
     folded into the record build / gradient unpack kernels.
+
+    ``compensation`` [N] (the projection's fifth output) selects the antialiased mode: the call is this one on
+    :func:`antialiased_opacities` ``(opacity_logits, compensation)`` with the logit flag off — same node, same kernels.
+    A caller with several passes over one render forms that tensor once and passes it as ``opacity_logits`` with
+    ``opacity_is_logit=False`` (what :func:`sgn_rast.step.render_fused` does).
 
     ``id_range=(lo, hi)`` renders only Gaussians ``lo <= id < hi`` of the SAME tensors — the scene graph's
     objects-only / background-only accumulation passes (``sgn_splatfacto_scene_graph.py:364-366``), which the
@@ -427,6 +476,11 @@ def rasterize_gaussians_fused(xys, depths, radii, conics, num_tiles_hit, colors,
     assert block_width > 1 and block_width <= 16, "block_width must be between 2 and 16"
     if background is None:
         background = torch.ones(3, dtype=torch.float32, device=colors.device)
+    if compensation is not None:
+        if not opacity_is_logit:
+            raise ValueError("compensation multiplies the sigmoid of LOGITS: opacity_is_logit=False does not go with it")
+        opacity_logits, opacity_is_logit = antialiased_opacities(opacity_logits, compensation), False
+    logit = bool(opacity_is_logit)
     args = (xys.contiguous(), depths.contiguous(), radii.contiguous(), conics.contiguous(), num_tiles_hit.contiguous(),
             colors.contiguous(), opacity_logits.contiguous(), img_height, img_width, block_width, background.contiguous())
     _ops._call_state.grad = torch.is_grad_enabled()
@@ -438,20 +492,20 @@ def rasterize_gaussians_fused(xys, depths, radii, conics, num_tiles_hit, colors,
             # one group is empty (a frame without a visible object): the other one's pass IS the main pass — its
             # accumulation is the alpha image itself, the empty group's is zero.  (Carried through the group kernel, the
             # empty group would never finish and keep every tile's walk alive to the end of its list.)
-            main = _RasterizeGaussians.apply(*args, True, True, None, bool(depth_channel))
+            main = _RasterizeGaussians.apply(*args, True, logit, None, bool(depth_channel))
             zero = torch.zeros(img_height, img_width, dtype=torch.float32, device=xys.device)
             accs = (zero, main[1]) if s == 0 else (main[1], zero)
             return main[0], main[1], (main[2] if depth_channel else None), accs[0], accs[1]
         if group_accumulation_enabled and block_width == 16:
-            out = _RasterizeGaussians.apply(*args, True, True, None, bool(depth_channel), False, None, s)
+            out = _RasterizeGaussians.apply(*args, True, logit, None, bool(depth_channel), False, None, s)
             # (the drop-in surface's own policy — option depth_channel=on — may have accumulated the channel unasked)
             return out[0], out[1], (out[2] if depth_channel else None), out[3], out[4]
-        main = _RasterizeGaussians.apply(*args, True, True, None, bool(depth_channel))
-        accs = [_RasterizeGaussians.apply(*args, True, True, (lo, hi), False)[1] if hi > lo
+        main = _RasterizeGaussians.apply(*args, True, logit, None, bool(depth_channel))
+        accs = [_RasterizeGaussians.apply(*args, True, logit, (lo, hi), False)[1] if hi > lo
                 else torch.zeros(img_height, img_width, dtype=torch.float32, device=xys.device)
                 for lo, hi in ((0, s), (s, n))]
         return main[0], main[1], (main[2] if depth_channel else None), accs[0], accs[1]
-    return _RasterizeGaussians.apply(*args, return_alpha, True, id_range, bool(depth_channel))
+    return _RasterizeGaussians.apply(*args, return_alpha, logit, id_range, bool(depth_channel))
 
 
 from . import config as _config

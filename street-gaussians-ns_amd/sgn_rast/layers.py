@@ -20,10 +20,12 @@ stats = {"calls": 0, "own_lists": 0}
 
 def rasterize_layers(xys, depths, radii, conics, num_tiles_hit, colors, opacity_logits, img_height: int,
                      img_width: int, block_width: int, background: torch.Tensor, split: int,
-                     own_list: Optional[bool] = None):
+                     own_list: Optional[bool] = None, opacity_is_logit: bool = True):
     """-> ``(img [3,H,W,3], final_T [3,H,W], depth [H,W])`` for the layers all / ids < split / ids >= split; each layer's
     image (``C + T * background``) and transmittance are bit-equal to ``rasterize_gaussians_fused`` with that
-    ``id_range`` (``tests/test_gpu_layers.py``).  The binning is the whole scene's, shared with the binning cache."""
+    ``id_range`` (``tests/test_gpu_layers.py``).  The binning is the whole scene's, shared with the binning cache.
+    ``opacity_is_logit=False``: ``opacity_logits`` holds probabilities (the antialiased mode's
+    ``fused.antialiased_opacities``), as the same argument of ``rasterize_gaussians_fused``."""
     if block_width != 16:
         raise L.SgnRastError("the layered forward exists for 16x16 tiles only (block_width=16)")
     with torch.no_grad():
@@ -42,7 +44,7 @@ def rasterize_layers(xys, depths, radii, conics, num_tiles_hit, colors, opacity_
         D = torch.empty(H, W, **f32)
         tile_bounds = ((W + 15) // 16, (H + 15) // 16, 1)
         n_isect, ids, bins = (0, None, None) if n == 0 else _ops._bin_gaussians_cached(
-            n, xys, depths, radii, num_tiles_hit, tile_bounds, 16, conics, opacity_logits, True)
+            n, xys, depths, radii, num_tiles_hit, tile_bounds, 16, conics, opacity_logits, bool(opacity_is_logit))
         if n_isect < 1:                       # nothing on screen: every layer is empty (T = 1, image = background)
             img[:] = bg_c
             Ts.fill_(1.0)
@@ -59,7 +61,8 @@ def rasterize_layers(xys, depths, radii, conics, num_tiles_hit, colors, opacity_
             stats["own_lists"] += 1
         recs = L.workspace(lib.sgn_raster_workspace_bytes(n, n_isect, L.C.byref(ro)), dev)
         L.check(lib.sgn_raster_layers_fwd(
-            H, W, 16, n, n_isect, L.ptr(ids), L.ptr(bins), L.ptr(xys_c), L.ptr(conics_c), L.ptr(colors_c), L.ptr(opac_c), 1,
+            H, W, 16, n, n_isect, L.ptr(ids), L.ptr(bins), L.ptr(xys_c), L.ptr(conics_c), L.ptr(colors_c), L.ptr(opac_c),
+            int(bool(opacity_is_logit)),
             L.ptr(bg_c), L.ptr(depths_c), split, L.ptr(own_ids), L.ptr(own_bins), L.ptr(img), L.ptr(Ts), L.ptr(D),
             L.ptr(recs), recs.numel(), 0, L.ptr(order), L.C.byref(ro), L.stream_ptr()), "sgn_raster_layers_fwd")
         stats["calls"] += 1

@@ -47,6 +47,16 @@ def leaf_params(raw: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     return {k: v.detach().clone().requires_grad_(True) for k, v in raw.items()}
 
 
+def antialiased_mode(rasterize_mode: str) -> bool:
+    """``rasterize_mode`` ("classic" | "antialiased", the reference's config field, sgn_splatfacto.py:214-222) -> is it
+    the antialiased one; anything else raises ``ValueError`` as the reference does (:951), before anything is launched."""
+    if rasterize_mode == "classic":
+        return False
+    if rasterize_mode == "antialiased":
+        return True
+    raise ValueError(f"Unknown rasterize_mode: {rasterize_mode!r} (\"classic\" or \"antialiased\")")
+
+
 def _split_recat(t: torch.Tensor, counts, retain_grad: bool = False):
     """The scene graph's property setters (sgn_splatfacto_scene_graph.py:153-215): every projection output is split
     per sub-model (views; `retain_grad` on the xys views, which is what each sub-model's `after_train` reads) and
@@ -61,10 +71,14 @@ def _split_recat(t: torch.Tensor, counts, retain_grad: bool = False):
 
 def render(P: Dict[str, torch.Tensor], cam: Camera, sh_degree_to_use: int = 3, block_width: int = 16,
            background: Optional[torch.Tensor] = None, with_depth: bool = False, ops=_hip_ops,
-           retain_xys_grad: bool = True, split_counts=None, caller_syncs: bool = True) -> SimpleNamespace:
+           retain_xys_grad: bool = True, split_counts=None, caller_syncs: bool = True,
+           rasterize_mode: str = "classic") -> SimpleNamespace:
     """``split_counts``: per-sub-model Gaussian counts when the caller is the scene graph (its property setters split
     and re-concatenate every projection output).  ``caller_syncs``: also replay the two host syncs the reference's
-    own code performs per pass (`radii.sum() == 0` at :878, `assert (num_tiles_hit > 0).any()` at :944)."""
+    own code performs per pass (`radii.sum() == 0` at :878, `assert (num_tiles_hit > 0).any()` at :944).
+    ``rasterize_mode="antialiased"``: the opacities are the reference's own commented-out expression (:947),
+    ``torch.sigmoid(opacities) * comp[:, None]``, with autograd through the projection's compensation output."""
+    antialiased = antialiased_mode(rasterize_mode)
     dev = P["means"].device
     H, W = cam.height, cam.width
     if background is None:
@@ -72,7 +86,7 @@ def render(P: Dict[str, torch.Tensor], cam: Camera, sh_degree_to_use: int = 3, b
     scales = torch.exp(P["log_scales"])                                          # :857
     colors = torch.cat((P["features_dc"], P["features_rest"]), dim=1)            # :858
     quats = P["quats"] / P["quats"].norm(dim=-1, keepdim=True)                   # :864
-    xys, depths, radii, conics, _comp, num_tiles_hit, _cov3d = ops.project_gaussians(  # :860-873
+    xys, depths, radii, conics, comp, num_tiles_hit, _cov3d = ops.project_gaussians(   # :860-873
         P["means"], scales, 1, quats, cam.viewmat[:3, :], cam.fx, cam.fy, cam.cx, cam.cy, H, W, block_width)
     out = SimpleNamespace()
     if split_counts is not None:                       # tuple-assign through the scene graph's setters, in order
@@ -81,6 +95,8 @@ def render(P: Dict[str, torch.Tensor], cam: Camera, sh_degree_to_use: int = 3, b
         radii, out.radii_parts = _split_recat(radii, split_counts)
         conics, out.conics_parts = _split_recat(conics, split_counts)
         num_tiles_hit, out.num_tiles_hit_parts = _split_recat(num_tiles_hit, split_counts)
+        if antialiased:
+            comp, out.comp_parts = _split_recat(comp, split_counts)
     out.xys, out.depths, out.radii, out.conics, out.num_tiles_hit = xys, depths, radii, conics, num_tiles_hit
     if caller_syncs and bool(radii.sum() == 0):                                  # :878 (host sync)
         # the reference's empty outputs (:879-886): background colour, zero accumulation / depth, no autograd graph
@@ -98,7 +114,10 @@ def render(P: Dict[str, torch.Tensor], cam: Camera, sh_degree_to_use: int = 3, b
     rgbs = torch.clamp(rgbs + 0.5, min=0.0)                                      # :940
     if caller_syncs:
         assert (num_tiles_hit > 0).any()                                         # :944 (host sync)
-    opacities = torch.sigmoid(P["opacity_logits"])                               # :949
+    if antialiased:
+        opacities = torch.sigmoid(P["opacity_logits"]) * comp.reshape(-1, *P["opacity_logits"].shape[1:])   # :947
+    else:
+        opacities = torch.sigmoid(P["opacity_logits"])                           # :949
     rgb, alpha = ops.rasterize_gaussians(                                        # :954-967
         xys, depths, radii, conics, num_tiles_hit, rgbs, opacities, H, W, block_width,
         background=background, return_alpha=True)
@@ -115,25 +134,35 @@ def render_fused(P: Dict[str, torch.Tensor], cam: Camera, sh_degree_to_use: int 
                  background: Optional[torch.Tensor] = None, with_depth: bool = False,
                  object_ids: Optional[torch.Tensor] = None, poses: Optional[torch.Tensor] = None,
                  idft: Optional[torch.Tensor] = None, depth_channel: bool = True,
-                 group_split: Optional[int] = None) -> SimpleNamespace:
+                 group_split: Optional[int] = None, rasterize_mode: str = "classic") -> SimpleNamespace:
     """Same result as :func:`render` on the scene-graph-aggregated parameters, through the fused front
     ends (:mod:`sgn_rast.fused`): raw parameters in, no activation / concat / transform kernels.
     ``P["means"]`` / ``P["quats"]`` are in each object's LOCAL frame when ``object_ids``/``poses`` are given;
-    ``P["features_dc"]`` is [N,F,3] with F Fourier coefficients weighted by ``idft[object]``."""
+    ``P["features_dc"]`` is [N,F,3] with F Fourier coefficients weighted by ``idft[object]``.
+    ``rasterize_mode="antialiased"``: ``fused.antialiased_opacities(logits, compensation)`` is formed once and every
+    pass takes that one tensor as probabilities; ``out.opacities`` holds it (what a caller's further passes over the
+    same render — ``features.rasterize_features``, ``expected_depth`` — take with ``opacity_is_logit=False``)."""
     from . import fused
+    antialiased = antialiased_mode(rasterize_mode)
     dev = P["means"].device
     H, W = cam.height, cam.width
     if background is None:
         background = _zeros3(dev)
-    xys, depths, radii, conics, _comp, num_tiles_hit, _cov3d = fused.project_gaussians_fused(
+    xys, depths, radii, conics, comp, num_tiles_hit, _cov3d = fused.project_gaussians_fused(
         P["means"], P["log_scales"], P["quats"], cam.viewmat[:3, :], cam.fx, cam.fy, cam.cx, cam.cy, H, W,
         block_width, object_ids=object_ids, poses=poses)
     out = SimpleNamespace(xys=xys, depths=depths, radii=radii, conics=conics, num_tiles_hit=num_tiles_hit)
     if xys.requires_grad:
         xys.retain_grad()
+    # the opacity argument of every pass below: the logits (sigmoid inside the row build), or the antialiased mode's
+    # effective opacities — ONE tensor, so the binning cache keeps hitting and autograd sums the passes' gradients
+    opac, logit = P["opacity_logits"], True
+    if antialiased:
+        opac = out.opacities = fused.antialiased_opacities(P["opacity_logits"], comp)
+        logit = False
     # start the binning now: its host read-back then overlaps the SH evaluation queued below
-    _hip_ops.prefetch_binning(xys, depths, radii, conics, num_tiles_hit, P["opacity_logits"], H, W, block_width,
-                              opacity_is_logit=True)
+    _hip_ops.prefetch_binning(xys, depths, radii, conics, num_tiles_hit, opac, H, W, block_width,
+                              opacity_is_logit=logit)
     # SH view directions use WORLD means (scene_graph.py:355): the kernel applies the pose itself
     rgbs = fused.spherical_harmonics_fused(sh_degree_to_use, P["means"], cam.cam_pos, P["features_dc"],
                                            P["features_rest"], object_ids=object_ids, idft=idft, poses=poses)
@@ -142,23 +171,24 @@ def render_fused(P: Dict[str, torch.Tensor], cam: Camera, sh_degree_to_use: int 
         # `group_split`, so do the accumulations of the ids below / from the split (the scene graph's two sub-model passes)
         if group_split is not None:
             rgb, alpha, depth_im, out.acc_head, out.acc_tail = fused.rasterize_gaussians_fused(
-                xys, depths, radii, conics, num_tiles_hit, rgbs, P["opacity_logits"], H, W, block_width,
-                background=background, return_alpha=True, depth_channel=True, group_split=group_split)
+                xys, depths, radii, conics, num_tiles_hit, rgbs, opac, H, W, block_width,
+                background=background, return_alpha=True, depth_channel=True, group_split=group_split,
+                opacity_is_logit=logit)
         else:
             rgb, alpha, depth_im = fused.rasterize_gaussians_fused(
-                xys, depths, radii, conics, num_tiles_hit, rgbs, P["opacity_logits"], H, W, block_width,
-                background=background, return_alpha=True, depth_channel=True)
+                xys, depths, radii, conics, num_tiles_hit, rgbs, opac, H, W, block_width,
+                background=background, return_alpha=True, depth_channel=True, opacity_is_logit=logit)
         out.rgb, out.alpha, out.rgbs = rgb, alpha, rgbs
         out.depth = torch.where(alpha[..., None] > 1e-3, depth_im[..., None] / alpha[..., None], 10)   # :995
         return out
-    rgb, alpha = fused.rasterize_gaussians_fused(xys, depths, radii, conics, num_tiles_hit, rgbs,
-                                                 P["opacity_logits"], H, W, block_width, background=background,
-                                                 return_alpha=True)
+    rgb, alpha = fused.rasterize_gaussians_fused(xys, depths, radii, conics, num_tiles_hit, rgbs, opac, H, W,
+                                                 block_width, background=background, return_alpha=True,
+                                                 opacity_is_logit=logit)
     out.rgb, out.alpha, out.rgbs = rgb, alpha, rgbs
     if with_depth:
         depth_im = fused.rasterize_gaussians_fused(
-            xys, depths, radii, conics, num_tiles_hit, depths[:, None].repeat(1, 3), P["opacity_logits"], H, W,
-            block_width, _zeros3(dev))[..., 0:1]
+            xys, depths, radii, conics, num_tiles_hit, depths[:, None].repeat(1, 3), opac, H, W,
+            block_width, _zeros3(dev), opacity_is_logit=logit)[..., 0:1]
         out.depth = torch.where(alpha[..., None] > 1e-3, depth_im / alpha[..., None], 10)
     return out
 
@@ -229,9 +259,10 @@ def _world_scene_params(models, poses: torch.Tensor, idft: torch.Tensor):
 
 
 def _submodel_raster(models, world_means, dcs, out, sub, cam: Camera, sh_degree_to_use: int, block_width: int,
-                     background: torch.Tensor, ops, caller_syncs: bool):
+                     background: torch.Tensor, ops, caller_syncs: bool, antialiased: bool = False):
     """``get_submodel_output`` (:255-303) for the sub-models ``sub`` up to its rasterization -> (rgb, alpha) of the
-    drop-in operator; ``out`` holds the per-model splits of the main projection."""
+    drop-in operator; ``out`` holds the per-model splits of the main projection (``antialiased``: the compensation's
+    among them, aggregated like the others)."""
     # get_submodel_output (:255-303): per-model tensors are aggregated with torch.cat — the geometry from the
     # per-model SPLITS of the main projection (copies again), the parameters from the sub-models themselves
     agg = lambda parts: torch.cat([parts[i] for i in sub], dim=0)               # aggregate_submodel_var :249-253
@@ -251,20 +282,25 @@ def _submodel_raster(models, world_means, dcs, out, sub, cam: Camera, sh_degree_
     rgbs = torch.clamp(ops.spherical_harmonics(sh_degree_to_use, viewdirs, colors) + 0.5, min=0.0)  # :939
     if caller_syncs:
         assert (out.num_tiles_hit > 0).any()                                         # :944 (self.num_tiles_hit)
-    return ops.rasterize_gaussians(xys_s, depths_s, radii_s, conics_s, nth_s, rgbs, torch.sigmoid(opac_s), cam.height,
+    opacities = torch.sigmoid(opac_s)                                                # :949
+    if antialiased:
+        opacities = opacities * agg(out.comp_parts).reshape(-1, *opac_s.shape[1:])   # :947
+    return ops.rasterize_gaussians(xys_s, depths_s, radii_s, conics_s, nth_s, rgbs, opacities, cam.height,
                                    cam.width, block_width, background=background, return_alpha=True)   # :954-967
 
 
 def render_scene_graph(models, poses: torch.Tensor, idft: torch.Tensor, cam: Camera, sh_degree_to_use: int = 3,
                        block_width: int = 16, ops=_hip_ops, fused: bool = False,
-                       caller_syncs: bool = True, sh_parts: bool = True, groups: bool = True) -> SimpleNamespace:
+                       caller_syncs: bool = True, sh_parts: bool = True, groups: bool = True,
+                       rasterize_mode: str = "classic") -> SimpleNamespace:
     """Replay of ``SplatfactoSceneGraphModel.get_outputs`` in training mode
     (``sgn_splatfacto_scene_graph.py:305-366``): ``models[0]`` is the background, ``models[i>0]`` rigid objects
     whose parameters live in the object's local frame; ``poses[i]`` = [R(9) t(3) q_o2w(4)], ``idft[i]`` = Fourier
     weights of the frame.  Four raster passes like the reference: rgb+alpha, depth, objects-only accumulation,
     background-only accumulation.  ``fused=True`` runs the main pass through :mod:`sgn_rast.fused` (no transform /
     activation / concat kernels) and skips the SH evaluation whose result the reference throws away in the two
-    accumulation passes (``:285``)."""
+    accumulation passes (``:285``).  ``rasterize_mode``: as :func:`render` / :func:`render_fused`, in every pass."""
+    antialiased = antialiased_mode(rasterize_mode)
     dev = models[0]["means"].device
     H, W = cam.height, cam.width
     counts = [m["means"].shape[0] for m in models]
@@ -276,15 +312,16 @@ def render_scene_graph(models, poses: torch.Tensor, idft: torch.Tensor, cam: Cam
         # `groups`: object_acc / background_acc ride on the main pass's walk (rasterize_gaussians_fused(group_split));
         # False keeps the round-3 form, two more id-range passes, for A/B and for the tests
         out = render_fused(P, cam, sh_degree_to_use, block_width, with_depth=True, object_ids=object_ids,
-                           poses=poses, idft=idft_p, group_split=counts[0] if groups else None)
+                           poses=poses, idft=idft_p, group_split=counts[0] if groups else None,
+                           rasterize_mode=rasterize_mode)
         if groups:
             out.object_acc, out.background_acc = out.acc_tail, out.acc_head                 # :364-366
             return out
-        opac_arg, raster = P["opacity_logits"], F_.rasterize_gaussians_fused
+        opac_arg, raster = (out.opacities if antialiased else P["opacity_logits"]), F_.rasterize_gaussians_fused
     else:
         P, world_means, dcs = _world_scene_params(models, poses, idft)
         out = render(P, cam, sh_degree_to_use, block_width, with_depth=True, ops=ops,   # :363
-                     split_counts=counts, caller_syncs=caller_syncs)
+                     split_counts=counts, caller_syncs=caller_syncs, rasterize_mode=rasterize_mode)
         if getattr(out, "empty", False):        # nothing visible: the sub-model passes return their empty outputs too
             out.object_acc = torch.zeros(H, W, device=dev)
             out.background_acc = torch.zeros(H, W, device=dev)
@@ -299,10 +336,11 @@ def render_scene_graph(models, poses: torch.Tensor, idft: torch.Tensor, cam: Cam
             # main pass's binning (one-entry cache) instead of slicing and sorting again
             rgbs = _zero_colors(sum(counts), dev)
             _, acc = raster(out.xys, out.depths, out.radii, out.conics, out.num_tiles_hit, rgbs, opac_arg, H, W,
-                            block_width, background=bg_zero, return_alpha=True, id_range=(lo, hi))
+                            block_width, background=bg_zero, return_alpha=True, id_range=(lo, hi),
+                            opacity_is_logit=not antialiased)
             return acc
         return _submodel_raster(models, world_means, dcs, out, range(*which), cam, sh_degree_to_use, block_width, bg_zero,
-                                ops, caller_syncs)[1]
+                                ops, caller_syncs, antialiased)[1]
 
     n_bg = counts[0]
     out.object_acc = submodel_acc(n_bg, sum(counts), (1, len(models)))                   # :364-365
@@ -330,22 +368,26 @@ def _eval_nothing_visible(H: int, W: int, background: torch.Tensor, sky: Optiona
 
 
 def render_eval(P: Dict[str, torch.Tensor], cam: Camera, background: torch.Tensor, sky: Optional[torch.Tensor] = None,
-                sh_degree: int = 3, block_width: int = 16, fused: bool = True, ops=_hip_ops) -> Dict[str, torch.Tensor]:
+                sh_degree: int = 3, block_width: int = 16, fused: bool = True, ops=_hip_ops,
+                rasterize_mode: str = "classic") -> Dict[str, torch.Tensor]:
     """``SplatfactoModel.get_outputs`` as ``get_outputs_for_camera`` reaches it: ``self.training == False`` under
     ``torch.no_grad()`` — the full SH degree whatever the step (sgn_splatfacto.py:937-938), a sky image looked up without
     jitter (``sky`` [H,W,3], e.g. ``sgn_rast.sky.sky_color(base, ..., jitter=None)``; None: ``use_sky_sphere=False``) and
     the final ``rgb.clamp(0, 1)`` (:974-975).  Returns the reference's keys: ``rgb`` [H,W,3], ``accumulation`` [H,W,1],
     ``depth`` [H,W,1] and ``sky`` when given.  ``fused=False`` is the call-site replay on the drop-in operators (or the
-    oracle's, ``ops``); ``fused=True`` the fused front ends with the depth channel riding in the colour pass."""
+    oracle's, ``ops``); ``fused=True`` the fused front ends with the depth channel riding in the colour pass.
+    ``rasterize_mode``: as :func:`render` / :func:`render_fused`."""
+    antialiased_mode(rasterize_mode)
     H, W = cam.height, cam.width
     with torch.no_grad():
         if fused:
-            out = render_fused(P, cam, sh_degree, block_width, background=background, with_depth=True)
+            out = render_fused(P, cam, sh_degree, block_width, background=background, with_depth=True,
+                               rasterize_mode=rasterize_mode)
             if bool(out.radii.sum() == 0):                                             # :878
                 return _eval_nothing_visible(H, W, background, sky)
         else:
             out = render(P, cam, sh_degree, block_width, background=background, with_depth=True, ops=ops,
-                         retain_xys_grad=False)
+                         retain_xys_grad=False, rasterize_mode=rasterize_mode)
             if getattr(out, "empty", False):
                 return _eval_nothing_visible(H, W, background, sky)
         rgb, alpha = _eval_finish(out.rgb, out.alpha, sky)
@@ -357,7 +399,8 @@ def render_eval(P: Dict[str, torch.Tensor], cam: Camera, background: torch.Tenso
 
 def render_scene_graph_eval(models, poses: torch.Tensor, idft: torch.Tensor, cam: Camera, background: torch.Tensor,
                             sky: Optional[torch.Tensor] = None, sh_degree: int = 3, block_width: int = 16,
-                            fused: bool = True, ops=_hip_ops, layered: bool = True) -> Dict[str, torch.Tensor]:
+                            fused: bool = True, ops=_hip_ops, layered: bool = True,
+                            rasterize_mode: str = "classic") -> Dict[str, torch.Tensor]:
     """``SplatfactoSceneGraphModel.get_outputs`` in EVAL mode (``self.training == False`` under ``torch.no_grad()``:
     what the reference's render / eval scripts and the trainer's eval image go through) — :func:`render_eval`'s semantics
     for the scene, the two sub-model accumulations, and the two decomposition images of
@@ -373,7 +416,9 @@ def render_scene_graph_eval(models, poses: torch.Tensor, idft: torch.Tensor, cam
     (:func:`sgn_rast.layers.rasterize_layers`) and one finishing launch.  ``layered=False`` keeps the fused front ends
     but renders the way the training-side API allows — the main pass with the depth channel and the two group
     accumulations, two more ``id_range`` colour passes, torch expressions after them — for A/B runs and for the tests: the
-    layered call returns the same bits."""
+    layered call returns the same bits.  ``rasterize_mode``: as :func:`render` / :func:`render_fused`, in every pass and
+    layer."""
+    antialiased = antialiased_mode(rasterize_mode)
     dev = models[0]["means"].device
     H, W = cam.height, cam.width
     # "prevent empty object" (:338-339): a model without points takes no part in the frame
@@ -409,21 +454,25 @@ def render_scene_graph_eval(models, poses: torch.Tensor, idft: torch.Tensor, cam
         if fused:
             from . import fused as F_, layers
             P, object_ids, idft_p = _fused_scene_params(models, idft)
-            xys, depths, radii, conics, _comp, num_tiles_hit, _cov3d = F_.project_gaussians_fused(
+            xys, depths, radii, conics, comp, num_tiles_hit, _cov3d = F_.project_gaussians_fused(
                 P["means"], P["log_scales"], P["quats"], cam.viewmat[:3, :], cam.fx, cam.fy, cam.cx, cam.cy, H, W,
                 block_width, object_ids=object_ids, poses=poses)
-            _hip_ops.prefetch_binning(xys, depths, radii, conics, num_tiles_hit, P["opacity_logits"], H, W, block_width,
-                                      opacity_is_logit=True)
+            opac, logit = P["opacity_logits"], True          # (one opacity tensor for every pass, as render_fused)
+            if antialiased:
+                opac, logit = F_.antialiased_opacities(P["opacity_logits"], comp), False
+            _hip_ops.prefetch_binning(xys, depths, radii, conics, num_tiles_hit, opac, H, W, block_width,
+                                      opacity_is_logit=logit)
             rgbs = F_.spherical_harmonics_fused(sh_degree, P["means"], cam.cam_pos, P["features_dc"],
                                                 P["features_rest"], object_ids=object_ids, idft=idft_p, poses=poses)
             if bool(radii.sum() == 0):                                                 # :878
                 return nothing_visible()
             if not layered:
-                geo = (xys, depths, radii, conics, num_tiles_hit, rgbs, P["opacity_logits"], H, W, block_width)
+                geo = (xys, depths, radii, conics, num_tiles_hit, rgbs, opac, H, W, block_width)
                 img_all, alpha, D, acc_h, acc_t = F_.rasterize_gaussians_fused(
-                    *geo, background=background, return_alpha=True, depth_channel=True, group_split=n_bg)
+                    *geo, background=background, return_alpha=True, depth_channel=True, group_split=n_bg,
+                    opacity_is_logit=logit)
                 part = lambda lo, hi: (F_.rasterize_gaussians_fused(*geo, background=background, return_alpha=True,
-                                                                    id_range=(lo, hi))[0]
+                                                                    id_range=(lo, hi), opacity_is_logit=logit)[0]
                                        if hi > lo else background.repeat(H, W, 1))
                 rgb, a = _eval_finish(img_all, alpha, sky)
                 res = {"rgb": rgb, "accumulation": a, "depth": torch.where(a > 1e-3, D[..., None] / a, 10)}   # :995
@@ -437,8 +486,8 @@ def render_scene_graph_eval(models, poses: torch.Tensor, idft: torch.Tensor, cam
                     res["object_acc"] = acc_t[..., None]
                     res["object_rgb"] = _eval_finish(part(n_bg, n_all), acc_t, None)[0]
                 return res
-            img, Ts, D = layers.rasterize_layers(xys, depths, radii, conics, num_tiles_hit, rgbs, P["opacity_logits"],
-                                                 H, W, block_width, background, n_bg)
+            img, Ts, D = layers.rasterize_layers(xys, depths, radii, conics, num_tiles_hit, rgbs, opac, H, W, block_width,
+                                                 background, n_bg, opacity_is_logit=logit)
             rgb3, acc3, depth = layers.finish(img, Ts, D, sky)
             res = {"rgb": rgb3[0], "accumulation": acc3[0][..., None], "depth": depth[..., None]}
             if sky is not None:
@@ -451,7 +500,7 @@ def render_scene_graph_eval(models, poses: torch.Tensor, idft: torch.Tensor, cam
             return res
         Pw, world_means, dcs = _world_scene_params(models, poses, idft)
         out = render(Pw, cam, sh_degree, block_width, background=background, with_depth=True, ops=ops,   # :363
-                     split_counts=counts, retain_xys_grad=False)
+                     split_counts=counts, retain_xys_grad=False, rasterize_mode=rasterize_mode)
         if getattr(out, "empty", False):
             return nothing_visible()
         rgb, alpha = _eval_finish(out.rgb, out.alpha, sky)
@@ -459,7 +508,7 @@ def render_scene_graph_eval(models, poses: torch.Tensor, idft: torch.Tensor, cam
         if sky is not None:
             res["sky"] = sky
         sub = lambda which: _submodel_raster(models, world_means, dcs, out, range(*which), cam, sh_degree, block_width,
-                                             background, ops, True)
+                                             background, ops, True, antialiased)
         objects, backgr = (1, len(models)), (0, 1)
         if not no_objects:
             res["object_acc"] = sub(objects)[1][..., None]                             # :364-365
@@ -505,7 +554,8 @@ def train_step(P: Dict[str, torch.Tensor], cam: Camera, w_img: torch.Tensor, w_a
                reducer=None, fused: bool = False, sky: Optional[dict] = None, gt: Optional[torch.Tensor] = None,
                ssim_lambda: float = 0.2, loss_fn=None, caller_syncs: bool = False, zero_grad: bool = True,
                mask: Optional[torch.Tensor] = None, lidar_depth: Optional[torch.Tensor] = None,
-               depth_loss_mult: float = 0.1, depth_loss_kind: str = "l1", **fused_kw) -> SimpleNamespace:
+               depth_loss_mult: float = 0.1, depth_loss_kind: str = "l1", rasterize_mode: str = "classic",
+               **fused_kw) -> SimpleNamespace:
     """One "train-step image": project fwd -> SH fwd -> rasterize(return_alpha) fwd -> scalar loss ->
     full backward to means / log-scales / raw quats / opacity logits / SH coefficients (the metric's definition,
     SURVEY.md §8d: the operator sequence; ``caller_syncs=True`` adds the two host syncs of the reference's own model
@@ -518,7 +568,9 @@ def train_step(P: Dict[str, torch.Tensor], cam: Camera, w_img: torch.Tensor, w_a
     ``lidar_depth`` [H,W] float32 (``sgn_rast.lidar.splat_depth``; 0 = no return) adds the LiDAR depth term
     ``depth_loss_mult * lidar.depth_loss(*features.expected_depth(...), lidar_depth, depth_loss_kind, mask)``: the
     expected depth is composited over the list the RGB pass binned (nothing is binned again) and ``out.depth_loss`` holds
-    the term's value; an empty view contributes nothing."""
+    the term's value; an empty view contributes nothing.  ``rasterize_mode="antialiased"`` multiplies the opacities by
+    the projection's compensation factor (:func:`render` / :func:`render_fused`), in the LiDAR term's pass too."""
+    antialiased = antialiased_mode(rasterize_mode)
     if mask is not None:           # host-side errors first: before the render, let alone the loss, launches anything
         if gt is None:
             raise ValueError("mask applies to the photometric loss: pass gt as well")
@@ -540,10 +592,11 @@ def train_step(P: Dict[str, torch.Tensor], cam: Camera, w_img: torch.Tensor, w_a
         if sky is not None:
             sky["base"].grad = None
     if fused:
-        out = render_fused(P, cam, sh_degree_to_use, block_width, with_depth=with_depth, **fused_kw)
+        out = render_fused(P, cam, sh_degree_to_use, block_width, with_depth=with_depth, rasterize_mode=rasterize_mode,
+                           **fused_kw)
     else:
         out = render(P, cam, sh_degree_to_use, block_width, with_depth=with_depth, ops=ops,
-                     caller_syncs=caller_syncs)
+                     caller_syncs=caller_syncs, rasterize_mode=rasterize_mode)
     if sky is not None:
         composite_sky(out, cam, sky["base"], sky["c2w"], train=sky.get("train", True), fused=fused,
                       sky_fn=sky.get("fn"))
@@ -563,9 +616,10 @@ def train_step(P: Dict[str, torch.Tensor], cam: Camera, w_img: torch.Tensor, w_a
             out.depth_loss = torch.zeros((), device=loss.device)
         else:
             # the opacity tensor the RGB pass binned under: its list is reused
-            opac = P["opacity_logits"] if fused else out.opacities
+            logit = bool(fused) and not antialiased
+            opac = P["opacity_logits"] if logit else out.opacities
             dsum, acc = features.expected_depth(out.xys, out.depths, out.radii, out.conics, out.num_tiles_hit, opac,
-                                                cam.height, cam.width, block_width, opacity_is_logit=bool(fused))
+                                                cam.height, cam.width, block_width, opacity_is_logit=logit)
             term = lidar.depth_loss(dsum, acc, lidar_depth, depth_loss_kind, mask)
             loss = loss + depth_loss_mult * term
             out.depth_loss = term.detach()

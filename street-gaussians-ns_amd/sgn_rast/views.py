@@ -270,15 +270,30 @@ class _RasterViews(Function):
                 None, None, None, None)
 
 
+def _check_rasterize_mode(rasterize_mode: str) -> None:
+    """Host-side, before any device work: the batched entries render the classic mode only.  The antialiased mode's
+    factor is per (view, Gaussian) while ``sgn_rasterize_views_fwd_all`` repeats the per-Gaussian logits for every view
+    inside the C call — per-view opacities need a change in there."""
+    from .step import antialiased_mode
+    if antialiased_mode(rasterize_mode):
+        raise NotImplementedError(
+            'rasterize_mode="antialiased" is not available for batched views: the batched rasterize entry takes one '
+            "opacity logit per Gaussian and repeats it for every view, the compensation factor differs per view; "
+            "render the views one by one (step.render_fused / step.train_step) in this mode")
+
+
 def render_views(P: Dict[str, torch.Tensor], cams: Sequence[Camera], sh_degree_to_use: int = 3,
                  background: Optional[torch.Tensor] = None, with_depth: bool = False, block_width: int = BLOCK,
-                 object_ids=None, poses=None, idft=None, group_split=None, id_range=None) -> SimpleNamespace:
+                 object_ids=None, poses=None, idft=None, group_split=None, id_range=None,
+                 rasterize_mode: str = "classic") -> SimpleNamespace:
     """Render ``P`` (the raw leaves of :func:`sgn_rast.step.render_fused`: means, log_scales, quats, opacity_logits,
     features_dc [N,1,3], features_rest) from every camera of ``cams`` (1 to 16 :class:`scenes.Camera`, one image size)
     in one batched call.  Returns ``rgb [B,H,W,3]``, ``alpha [B,H,W]``, with ``with_depth`` also ``depth [B,H,W,1]``
     (as ``render_fused``), and the projection's ``xys [B,N,2]`` (gradient retained), ``depths``, ``radii``,
     ``conics``, ``num_tiles_hit`` as ``[B,N,...]`` (per view: feed ``densify.Stats.update`` with ``xys.grad[b]``,
-    ``radii[b]``).  View b equals ``render_fused(P, cams[b])`` bit for bit."""
+    ``radii[b]``).  View b equals ``render_fused(P, cams[b])`` bit for bit.  ``rasterize_mode``: "classic" only;
+    "antialiased" raises ``NotImplementedError`` (per-view compensation factors, see ``_check_rasterize_mode``)."""
+    _check_rasterize_mode(rasterize_mode)
     b, n, h, w = check_views(P, cams, block_width, object_ids=object_ids, poses=poses, idft=idft,
                              group_split=group_split, id_range=id_range)
     dev = P["means"].device
@@ -302,11 +317,14 @@ def render_views(P: Dict[str, torch.Tensor], cams: Sequence[Camera], sh_degree_t
 
 def train_step_views(P: Dict[str, torch.Tensor], cams: Sequence[Camera], gts: Sequence[torch.Tensor],
                      ssim_lambda: float = 0.2, sh_degree_to_use: int = 3, zero_grad: bool = True,
-                     masks: Optional[Sequence[Optional[torch.Tensor]]] = None) -> SimpleNamespace:
+                     masks: Optional[Sequence[Optional[torch.Tensor]]] = None,
+                     rasterize_mode: str = "classic") -> SimpleNamespace:
     """One multi-view step: :func:`render_views`, then the mean over the views of the per-view photometric loss of
     :mod:`sgn_rast.loss` ((1-l) L1 + l (1 - SSIM) on ``rgb.clamp(max=1)``, each view on its own: no SSIM window spans two
     views) — the data-parallel path's averaged-gradient semantics (``sgn_rast/dp.py``) on one GPU — and the backward.
-    ``masks``: one pixel mask per view (``sgn_rast.loss.l1_ssim``'s ``mask``; an entry may be ``None``)."""
+    ``masks``: one pixel mask per view (``sgn_rast.loss.l1_ssim``'s ``mask``; an entry may be ``None``).
+    ``rasterize_mode``: as :func:`render_views`."""
+    _check_rasterize_mode(rasterize_mode)
     from .loss import check_mask, photometric_loss
     if len(gts) != len(cams):
         raise ValueError(f"{len(cams)} cameras but {len(gts)} ground-truth images")
@@ -320,7 +338,7 @@ def train_step_views(P: Dict[str, torch.Tensor], cams: Sequence[Camera], gts: Se
     if zero_grad:
         for p in P.values():
             p.grad = None
-    out = render_views(P, cams, sh_degree_to_use)
+    out = render_views(P, cams, sh_degree_to_use, rasterize_mode=rasterize_mode)
     b = len(cams)
     loss = sum(photometric_loss(out.rgb[v], gts[v], ssim_lambda, clamp_max=1.0, mask=masks[v]) for v in range(b)) / b
     loss.backward()
