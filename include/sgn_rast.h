@@ -710,6 +710,32 @@ int sgn_raster_bwd_part(int img_h, int img_w, int block_width, int n, int64_t n_
                         const int32_t *tile_order, const float *colors_pre_clamp, const sgn_raster_opts *opts,
                         sgn_stream_t stream, sgn_stream_t aux_stream, int first, int last);
 
+/* sgn_raster_bwd_part with the ABSGRAD statistic (AbsGS; gsplat's `absgrad=True` / `means2d.absgrad`; no gsplat 0.1.x
+ * counterpart): besides the signed gradients, v_xy_abs [n,2] = per Gaussian the sum over the pixels its reverse walk
+ * composites it onto of the ABSOLUTE per-pixel screen-space gradient,
+ *     v_xy_abs[g] = sum_pixels ( |A p + B q|, |B p + C q| ),   (p, q) = v_sigma * (dx, dy),  (A, B, C) = conic[g]
+ * where the signed v_xy[g] is the same sum without the bars (so v_xy_abs >= |v_xy| up to rounding).  Densification that
+ * thresholds the norm of v_xy misses large splats over fine texture, whose per-pixel terms cancel; this does not.  fp32
+ * contract per evaluated (pixel, entry) pair: ax += fabsf(fmaf(A, p, B * q)), ay += fabsf(fmaf(B, p, C * q)), no
+ * contraction; the sums over a tile's pixels are a wave reduction and the sums over tiles float atomics, as for the
+ * signed gradients.  The signed outputs are those of sgn_raster_bwd_part (same body, same arithmetic, same order).
+ * Arguments as sgn_raster_bwd_part; window != 0 is an argument error (-13) and so is v_xy_abs == NULL (-14).
+ * The two sums live in slots 9 and 10 of a Gaussian's row of the packed gradient workspace (12 floats; the plain walks
+ * use slots 0-8 and leave the rest as the clear left them).  When several walks chain into one workspace (first / last),
+ * ONLY the walks issued through this entry add to slots 9 and 10 — a group-accumulation walk issued through
+ * sgn_raster_bwd_part contributes to the signed gradients alone — and the LAST walk must go through this entry for
+ * v_xy_abs (and the other four outputs) to be written: sgn_raster_bwd_part's unpack does not read those slots.  n == 0:
+ * nothing is written; n_isect == 0 with last != 0: zeros. */
+int sgn_raster_bwd_abs(int img_h, int img_w, int block_width, int n, int64_t n_isect,
+                       const int32_t *gaussian_ids_sorted, const int32_t *tile_bins, const float *xys,
+                       const float *conics, const float *colors, const float *opacities, int opacity_is_logit,
+                       int id_lo, int id_hi, int window, const float *background3, const float *final_Ts,
+                       const int32_t *final_idx, const float *v_out_img, const float *v_out_alpha,
+                       float alpha_clamp_bwd, float *v_xy, float *v_conic, float *v_colors, float *v_opacity,
+                       void *recs_ws, size_t recs_ws_bytes, int recs_packed, void *grad_ws, size_t grad_ws_bytes,
+                       const int32_t *tile_order, const float *colors_pre_clamp, const sgn_raster_opts *opts,
+                       sgn_stream_t stream, sgn_stream_t aux_stream, int first, int last, float *v_xy_abs /*[n,2]*/);
+
 /* The backward of a rasterize node as ONE call (round 6): sgn_tile_order over the forward's tile statistics (tile_order
  * [tiles + 2] out — NULL: no reordering, the in-kernel split of long walks —, long walks = opts->adapt_bwd, the
  * small-splat promotion small_q16 only when stats_have_pairs) + sgn_raster_bwd (first = last = 1; window allowed) or

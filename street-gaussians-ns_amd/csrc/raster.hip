@@ -76,19 +76,7 @@ __global__ __launch_bounds__(256) void build_grec_kernel(int n, const float *__r
     grec[3 * g + 2] = make_float4(bl, __int_as_float(g), ex, ey);
 }
 
-// pixel of (slot q, lane) inside tile (tx,ty).  block 16: four 8x8 quadrants; otherwise linear.
-__device__ __forceinline__ void slot_pixel(int q, int lane, int B, int &ox, int &oy, bool &in_tile) {
-    if (B == 16) {
-        ox = (q & 1) * 8 + (lane & 7);
-        oy = (q >> 1) * 8 + (lane >> 3);
-        in_tile = true;
-    } else {
-        const int p = q * 64 + lane;
-        ox = p % B;
-        oy = p / B;
-        in_tile = p < B * B;
-    }
-}
+// (slot_pixel — pixel of (slot q, lane) inside a tile — lives in raster_common.h with the backward body)
 
 
 // `recs` is the per-Gaussian row table and `ids` the sorted id list; the wave chases ids[k] -> row with two dependent
@@ -722,205 +710,8 @@ __global__ __launch_bounds__(64) void raster_fwd_pk_kernel(int W, int H, int til
     }
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-// The nine per-Gaussian partial gradients (REDUCE == 1) go through raster_common.h's transposed reduction: after the
-// 32- and 16-lane folds three registers hold, per 16-lane row, t0 = [v0 v2 v1 v3], t1 = [v4 v6 v5 v7], t2 = [v8 0 0 0];
-// four DPP adds finish each row.  28 cross-lane ops instead of 54 shuffles.
-
-// grad_ws row layout (12 floats / Gaussian): 0,1 m_x, m_y | 2,3,4 s_xx, s_xy, s_yy (raw moments; the conic is applied by
-// unpack_grads_kernel) | 5,6,7 v_rgb | 8 v_opacity
-template <bool EXACT, int REDUCE, int QPW, bool ADAPT>
-__device__ __forceinline__ void raster_bwd_tile(int tile, int wv, int W, int H, int B, int tiles_x,
-                                                const int2 *__restrict__ bins, const Rec *__restrict__ recs,
-                                                const int32_t *__restrict__ ids, const float *__restrict__ bg,
-                                                const float *__restrict__ final_T,
-                                                const int32_t *__restrict__ final_idx,
-                                                const float *__restrict__ v_out,
-                                                const float *__restrict__ v_out_alpha, float alpha_clamp,
-                                                float *__restrict__ grad_ws, int dbg, int adapt_thresh,
-                                                int batch_thresh, int use_qm) {
-    static_assert(!ADAPT || QPW == 4, "adaptive splitting starts from the 4-quadrant wave");
-    const bool qm_on = use_qm != 0 && B == 16;      // wave-uniform
-    const int idmask = qm_idmask(use_qm);
-    const int q0 = ADAPT ? 0 : wv * QPW;
-    const int lane = threadIdx.x;
-    const int2 range = bins[tile];
-    if (range.x >= range.y) return;
-    const int tx = tile % tiles_x, ty = tile / tiles_x;
-    const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
-
-    // Per-pixel state.  Algebra: with dotc = sum_c color_c * v_out_c (per pixel x Gaussian)
-    // and bv = sum_c buffer_c * v_out_c (maintained incrementally: bv += fac * dotc), upstream's
-    //   v_alpha = sum_c (color_c*T - buffer_c*ra) * v_out_c + T_final*ra*v_out_alpha - T_final*ra*sum_c bg_c*v_out_c
-    // becomes  v_alpha = ra * (T_before * dotc - bv + c0),  c0 = T_final * (v_out_alpha - sum_c bg_c*v_out_c),
-    // i.e. 3 VALU ops instead of ~26, one running scalar instead of a 3-channel buffer.
-    float px[QPW], py[QPW], T[QPW], c0[QPW], bv[QPW], vo0[QPW], vo1[QPW], vo2[QPW];
-    int kfin[QPW], pixi[QPW];
-    int kmax_l = -1;
-#pragma unroll
-    for (int q = 0; q < QPW; ++q) {          // phase 1: where does each pixel's walk start?
-        int ox, oy;
-        bool in_tile;
-        slot_pixel(q0 + q, lane, B, ox, oy, in_tile);
-        const int j = tx * B + ox, i = ty * B + oy;
-        const bool inside = in_tile && j < W && i < H;
-        pixi[q] = inside ? i * W + j : -1;
-        px[q] = (float)j + 0.5f;
-        py[q] = (float)i + 0.5f;
-        kfin[q] = inside ? final_idx[pixi[q]] : -1;  // -1: this slot never participates
-        kmax_l = max(kmax_l, kfin[q]);
-    }
-    int kmax = __builtin_amdgcn_readfirstlane(wave_max_i(kmax_l));
-    kmax = min(kmax, range.y - 1);
-    if (kmax < range.x) return;
-    if constexpr (ADAPT) {                   // split tiles whose reverse walk is long, one quadrant per wave
-        const bool split = (kmax - range.x + 1) >= adapt_thresh;
-        if (!split && wv != 0) return;
-        if (split) {
-            int km = -1;
-#pragma unroll
-            for (int q = 0; q < QPW; ++q) {
-                if (q != wv) { kfin[q] = -1; pixi[q] = -1; } else km = kfin[q];
-            }
-            kmax = min(__builtin_amdgcn_readfirstlane(wave_max_i(km)), range.y - 1);
-            if (kmax < range.x) return;
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < QPW; ++q) {          // phase 2: per-pixel state of the active slots
-        const bool inside = pixi[q] >= 0;
-        const int pix = inside ? pixi[q] : 0;
-        const float Tf = inside ? final_T[pix] : 1.f;
-        T[q] = Tf;
-        // A pixel nothing was composited onto (its transmittance stayed EXACTLY 1: the first composited entry makes it
-        // <= 254/255) takes no part in the reverse walk; upstream never reads its incoming gradients.  The body below is
-        // branch-free — a masked lane contributes `0 * v_out` — so a non-finite value there would reach the sums as
-        // 0 x NaN.  Such values are ordinary: `depth / alpha` under a `where(alpha > eps, ...)` (sgn_splatfacto.py:995)
-        // has gradient 0 / 0 on every uncovered pixel.  Their gradients are therefore not loaded at all (round 5).
-        const bool live = inside && Tf < 1.f;
-        // v_out == NULL: the image took no part in the loss (an accumulation-only pass): zeros, and no 29 MB read
-        vo0[q] = (live && v_out != nullptr) ? v_out[3 * pix] : 0.f;
-        vo1[q] = (live && v_out != nullptr) ? v_out[3 * pix + 1] : 0.f;
-        vo2[q] = (live && v_out != nullptr) ? v_out[3 * pix + 2] : 0.f;
-        const float voa = live ? v_out_alpha[pix] : 0.f;
-        c0[q] = Tf * (voa - fmaf(bg0, vo0[q], fmaf(bg1, vo1[q], bg2 * vo2[q])));
-        bv[q] = 0.f;
-    }
-
-    const bool qtest = (B == 16);
-    const float qcx = (float)(tx * 16 + (lane & 1) * 8) + 4.0f, qcy = (float)(ty * 16 + ((lane >> 1) & 1) * 8) + 4.0f;
-    bool kfin_active[QPW];   // wave-uniform: does any pixel of this slot take part in the reverse walk?
-#pragma unroll
-    for (int q = 0; q < QPW; ++q) kfin_active[q] = __ballot(kfin[q] >= range.x) != 0ull;
-
-    // one depth-list entry (reverse walk) for this wave's pixels
-    auto entry = [&](const Rec &cur, int k, unsigned qm) __attribute__((always_inline)) {
-        // Spatial terms as raw MOMENTS (r03): m = sum vs (dx, dy), s = sum vs (dx^2, dx dy, dy^2).  The conic that turns
-        // them into v_xy = (a m_x + b m_y, b m_x + c m_y) and v_conic = (s_xx / 2, s_xy, s_yy / 2) is a per-GAUSSIAN
-        // constant, so it is applied once per Gaussian in unpack_grads_kernel instead of once per (pixel, entry) here:
-        // 2 mul + 2 add + 3 fma in place of 4 mul + 7 fma.
-        float m_x = 0.f, m_y = 0.f, s_xx = 0.f, s_xy = 0.f, s_yy = 0.f;
-        float g_r = 0.f, g_g = 0.f, g_b = 0.f, g_o = 0.f;
-        bool any = false;
-#pragma unroll
-        for (int q = 0; q < QPW; ++q) {
-            if (!((qm >> (q0 + q)) & 1u) || __ballot(k <= kfin[q]) == 0ull) continue;  // wave-uniform
-            const float dx = cur.x - px[q], dy = cur.y - py[q];
-            const float t1 = cur.ha * dx, t2 = cur.hc * dy, t3 = cur.b * dx;
-            const float sigma = fmaf(t3, dy, fmaf(t2, dy, t1 * dx));
-            const float vis = sgn_exp<EXACT>(-sigma);
-            const float av = cur.opac * vis;
-            const float alpha = fminf(alpha_clamp, av);
-            const bool valid = (k <= kfin[q]) && sigma >= 0.f && alpha >= (1.f / 255.f);
-            // branch-free: everything is evaluated, invalid lanes are masked out by three selects.  (ONE select — an
-            // invalid lane continuing with vis = 0, so that alpha = 0, ra = 1, fac = 0, vs = 0 — was measured in r03:
-            // 3 % SLOWER on all three workloads; the select then sits in front of the rcp on the dependency chain.)
-            const float ra = __builtin_amdgcn_rcpf(1.f - alpha);   // v_rcp_f32 (1 ulp); oracle divides exactly
-            const float Tn = T[q] * ra;
-            const float fac = alpha * Tn;
-            const float dotc = fmaf(cur.r, vo0[q], fmaf(cur.g, vo1[q], cur.bl * vo2[q]));
-            const float v_alpha = ra * fmaf(T[q], dotc, c0[q] - bv[q]);
-            const float vm = valid ? v_alpha : 0.f;
-            const float facm = valid ? fac : 0.f;
-            bv[q] = fmaf(facm, dotc, bv[q]);
-            T[q] = valid ? Tn : T[q];
-            const float vs = -av * vm;                              // v_sigma (upstream: not zeroed by the clamp)
-            const float p = vs * dx, qq = vs * dy;
-            m_x += p;
-            m_y += qq;
-            s_xx = fmaf(p, dx, s_xx);
-            s_xy = fmaf(p, dy, s_xy);
-            s_yy = fmaf(qq, dy, s_yy);
-            g_r = fmaf(facm, vo0[q], g_r);
-            g_g = fmaf(facm, vo1[q], g_g);
-            g_b = fmaf(facm, vo2[q], g_b);
-            g_o = fmaf(vis, vm, g_o);
-            any = any || valid;
-        }
-        if (__ballot(any) != 0ull) {  // wave-uniform
-            if constexpr (REDUCE == 1) {
-                float t0 = fold16(fold32(m_x, m_y), fold32(s_xx, s_xy));     // rows: m_x, s_xx, m_y, s_xy
-                float t1 = fold16(fold32(s_yy, g_r), fold32(g_g, g_b));      // rows: s_yy, g, r, b
-                float t2 = fold16(fold32(g_o, 0.f), 0.f);                    // rows: o, 0, 0, 0
-                t0 = row_sum_dpp(t0); t1 = row_sum_dpp(t1); t2 = row_sum_dpp(t2);
-                const int c = lane & 15, row = lane >> 4;
-                const int rowmap = ((row & 1) << 1) | (row >> 1);            // rows 0,1,2,3 hold values 0,2,1,3
-                const float mine = (c == 0) ? t0 : (c == 1) ? t1 : t2;
-                if ((c < 2 || lane == 2) && !(dbg & 1))
-                    unsafeAtomicAdd(grad_ws + (size_t)cur.gid * SGN_RECORD_FLOATS + (c * 4 + rowmap), mine);
-            } else {
-                if (!(dbg & 2)) {          // dbg bit1: ablation only, skip the wave reduction (results are wrong)
-                    m_x = wave_sum(m_x); m_y = wave_sum(m_y);
-                    s_xx = wave_sum(s_xx); s_xy = wave_sum(s_xy); s_yy = wave_sum(s_yy);
-                    g_r = wave_sum(g_r); g_g = wave_sum(g_g); g_b = wave_sum(g_b);
-                    g_o = wave_sum(g_o);
-                }
-                float mine = m_x;
-                mine = (lane == 1) ? m_y : mine;
-                mine = (lane == 2) ? s_xx : mine;
-                mine = (lane == 3) ? s_xy : mine;
-                mine = (lane == 4) ? s_yy : mine;
-                mine = (lane == 5) ? g_r : mine;
-                mine = (lane == 6) ? g_g : mine;
-                mine = (lane == 7) ? g_b : mine;
-                mine = (lane == 8) ? g_o : mine;
-                if (lane < 9 && !(dbg & 1))  // dbg bit0: ablation, no atomics
-                    unsafeAtomicAdd(grad_ws + (size_t)cur.gid * SGN_RECORD_FLOATS + lane, mine);
-            }
-        }
-    };
-
-    // the reverse walk, kmax down to range.x: the forward's two ways through the list, downwards
-    const int L = kmax - range.x + 1;
-    if (L < batch_thresh) {
-        walk_chase<-1, false>(ids, recs, nullptr, idmask, kmax, range.x, [&](const Rec &cur, int raw, int k, float) {
-            entry(cur, k, qm_on ? qm_bits(raw, cur.ex) : quadrant_mask(cur, qcx, qcy, qtest));
-            return true;
-        });
-    } else {
-        __shared__ float4 stage[2][64 * 3];
-        unsigned mine_q = 0u;
-#pragma unroll
-        for (int q = 0; q < QPW; ++q)
-            if (kfin_active[q]) mine_q |= 1u << (q0 + q);
-        walk_staged<-1, false>(
-            ids, recs, nullptr, idmask, kmax, L, stage, nullptr,
-            [&](int raw, const float4 &r0, const float4 &r2) {
-                return (qm_on ? qm_bits(raw, r2.z) : row_quadrants(r0.x, r0.y, r2.z, r2.w, tx * 16, ty * 16, qtest)) & mine_q;
-            },
-            [](bool, int) {},
-            [&](const Rec &cur, int, int k, unsigned qm, float) {
-                entry(cur, k, qm);
-                return true;
-            });
-    }
-}
-
+// (wave_sum and raster_bwd_tile, the backward body, live in raster_common.h: raster_absgrad.hip instantiates the same
+// body with the absgrad statistic switched on)
 
 // Launch shapes of the backward.
 //   MODE 0: one workgroup per (tile, wave), the in-kernel adaptive split (QPW = 4, ADAPT): callers without a launch
@@ -1011,23 +802,8 @@ __global__ __launch_bounds__(256) void unpack_grads_kernel(int n, int row0, cons
     const float4 a = reinterpret_cast<const float4 *>(ws)[3 * (size_t)(row0 + i) + 0];
     const float4 b = reinterpret_cast<const float4 *>(ws)[3 * (size_t)(row0 + i) + 1];
     const float4 c = reinterpret_cast<const float4 *>(ws)[3 * (size_t)(row0 + i) + 2];
-    moments_to_grads(conics + 3 * i, a, b.x, v_xy + 2 * i, v_conic + 3 * i);
-    float v0 = b.y, v1 = b.z, v2 = b.w;
-    if (colors_pre != nullptr) {   // the colours were clamp(pre, min = 0): gradient w.r.t. `pre` (torch: grad * (pre >= 0))
-        v0 = colors_pre[3 * i] >= 0.f ? v0 : 0.f;
-        v1 = colors_pre[3 * i + 1] >= 0.f ? v1 : 0.f;
-        v2 = colors_pre[3 * i + 2] >= 0.f ? v2 : 0.f;
-    }
-    v_colors[3 * i] = v0; v_colors[3 * i + 1] = v1; v_colors[3 * i + 2] = v2;
-    float vo = c.x;
-    if (opac_is_logit == 1) {         // opac holds logits: chain through the fused sigmoid
-        const float sg = 1.f / (1.f + expf(-opac[i]));
-        vo = vo * sg * (1.f - sg);
-    } else if (opac_is_logit == 2) {  // opac holds sigmoid OUTPUTS, the gradient w.r.t. their logits is wanted
-        const float sg = opac[i];
-        vo = vo * sg * (1.f - sg);
-    }
-    v_opac[i] = vo;
+    // (the row's arithmetic is raster_common.h's unpack_row: raster_absgrad.hip's unpack shares it)
+    unpack_row(i, a, b, c, conics, opac, opac_is_logit, colors_pre, v_xy, v_conic, v_colors, v_opac);
 }
 
 // ---- batched views (include/sgn_rast.h "Batched views") -------------------------------------------------------------
@@ -1140,25 +916,6 @@ __global__ __launch_bounds__(256) void unpack_views_kernel(int n, int n_views, c
         vsum += c.x * sg * (1.f - sg);
     }
     v_opac[i] = vsum;
-}
-
-// Kernel-selection options arrive with every call (include/sgn_rast.h: sgn_raster_opts); NULL = defaults.
-sgn_raster_opts resolve_opts(const sgn_raster_opts *o) {
-    sgn_raster_opts r;
-    sgn_raster_default_opts(&r);
-    if (o) {
-        r = *o;
-        r.exact_exp = r.exact_exp ? 1 : 0;
-        r.reduce_mode = r.reduce_mode ? 1 : 0;
-        r.ids_qmask = r.ids_qmask ? 1 : 0;
-        sgn_raster_opts d;
-        sgn_raster_default_opts(&d);
-        if (r.adapt_fwd <= 0) r.adapt_fwd = d.adapt_fwd;
-        if (r.adapt_bwd <= 0) r.adapt_bwd = d.adapt_bwd;
-        if (r.batch_fwd <= 0) r.batch_fwd = d.batch_fwd;
-        if (r.batch_bwd <= 0) r.batch_bwd = d.batch_bwd;
-    }
-    return r;
 }
 
 }  // namespace

@@ -139,7 +139,13 @@ PARAM_NAMES = ("means", "log_scales", "quats", "features_dc", "features_rest", "
 
 @dataclass
 class DensifyConfig:
-    """The thresholds of ``SplatfactoModelConfig`` that ``refinement_after`` reads (sgn_splatfacto.py:153-226)."""
+    """The thresholds of ``SplatfactoModelConfig`` that ``refinement_after`` reads (sgn_splatfacto.py:153-226).
+
+    ``absgrad`` (AbsGS; gsplat's ``DefaultStrategy(absgrad=True)``; no counterpart in the reference): the statistic
+    ``after_train`` accumulates is the norm of ``xys.absgrad`` — the per-pixel screen-space gradients summed by
+    ABSOLUTE value (``fused.rasterize_gaussians_fused(absgrad=True)``) — instead of the norm of ``xys.grad``, whose
+    per-pixel terms cancel on large splats over fine texture.  The threshold stays ``densify_grad_thresh``; an
+    absolute sum is never smaller than the signed one, so AbsGS users RAISE it (gsplat suggests about 4x: 0.0008)."""
     warmup_length: int = 500
     refine_every: int = 100
     cull_alpha_thresh: float = 0.1
@@ -154,6 +160,7 @@ class DensifyConfig:
     stop_screen_size_at: int = 4000
     stop_split_at: int = 15000
     num_train_data: int = 0
+    absgrad: bool = False
 
 
 def _mix64(x: torch.Tensor) -> torch.Tensor:
@@ -223,11 +230,19 @@ class Densifier:
         self.record: Dict[str, float] = {}
 
     # ------------------------------------------------------------------------------------------------ after_train
-    def after_train(self, step: int, xys_grad: Optional[torch.Tensor], radii: torch.Tensor, last_size) -> None:
-        """:513-541 — accumulate this step's statistics (stops at ``stop_split_at`` like the reference)."""
+    def after_train(self, step: int, xys_grad: Optional[torch.Tensor], radii: torch.Tensor, last_size,
+                    absgrad: Optional[torch.Tensor] = None) -> None:
+        """:513-541 — accumulate this step's statistics (stops at ``stop_split_at`` like the reference).  Under
+        ``DensifyConfig(absgrad=True)`` the statistic is fed ``absgrad`` (the render's ``xys.absgrad``) instead of
+        ``xys_grad``; both None: the view saw nothing."""
         self.last_size = (int(last_size[0]), int(last_size[1]))
         if step >= self.cfg.stop_split_at:
             return
+        if self.cfg.absgrad:
+            if absgrad is None and xys_grad is not None:
+                raise ValueError("DensifyConfig(absgrad=True): after_train needs the render's xys.absgrad "
+                                 "(rasterize_gaussians_fused(absgrad=True))")
+            xys_grad = absgrad
         if xys_grad is None:                      # this rank's view saw nothing: zero gradient, nothing visible
             xys_grad = torch.zeros(radii.shape[0], 2, dtype=torch.float32, device=radii.device)
         self.stats.update(xys_grad, radii, self.last_size, step=step)
@@ -477,11 +492,14 @@ class SceneGraphDensifier:
         self.parts = [Densifier(m, optimizers, cfgs[i], seed=seed * 1009 + i, group=group,
                                 stats=stats_factory(group=group), **densifier_kw) for i, m in enumerate(models)]
 
-    def after_train(self, step: int, visible, xys_grads, radii_parts, last_size) -> None:
+    def after_train(self, step: int, visible, xys_grads, radii_parts, last_size, absgrads=None) -> None:
         """``visible``: indices of the sub-models in this step's render, in render order; ``xys_grads[j]`` /
-        ``radii_parts[j]``: the retained ``xys.grad`` (None: the view saw nothing) and the radii of ``visible[j]``."""
+        ``radii_parts[j]``: the retained ``xys.grad`` (None: the view saw nothing) and the radii of ``visible[j]``;
+        ``absgrads[j]``: its slice of ``xys.absgrad`` (``step.render_scene_graph(absgrad=True)``:
+        ``out.xys_absgrad_parts()``), which a sub-model configured with ``DensifyConfig(absgrad=True)`` reads instead."""
         for j, i in enumerate(visible):
-            self.parts[i].after_train(step, xys_grads[j], radii_parts[j], last_size)
+            self.parts[i].after_train(step, xys_grads[j], radii_parts[j], last_size,
+                                      absgrad=None if absgrads is None else absgrads[j])
 
     def refinement_after(self, step: int):
         """Every sub-model in model order (the same collectives in the same order on every rank).  Returns the list of

@@ -89,7 +89,7 @@ class _RasterizeFeatures(Function):
 
 def rasterize_features(xys, depths, radii, conics, num_tiles_hit, features, opacity, img_height: int, img_width: int,
                        block_width: int = 16, background: Optional[torch.Tensor] = None, return_alpha: bool = False,
-                       opacity_is_logit: bool = False):
+                       opacity_is_logit: bool = False, absgrad: bool = False):
     """Alpha-composite ``features [N,K]`` (1 <= K <= 64) over the depth list of these projection outputs ->
     ``out [H,W,K]`` or ``(out, alpha [H,W])``: per channel what ``rasterize_gaussians`` composites for a colour, bit for
     bit, from one walk of the lists per 16 channels.
@@ -103,7 +103,12 @@ def rasterize_features(xys, depths, radii, conics, num_tiles_hit, features, opac
     opacity`` it bins nothing.  Gradients go to ``xys``, ``conics``, ``features`` and ``opacity`` (none to ``depths``: it
     only orders the list); ``ops.semantics().alpha_clamp_bwd`` and the ``exact_exp`` option are read at call time.
     ``features`` may depend on the projection's outputs: ``depths[:, None]`` as a channel renders the expected depth,
-    whose gradient reaches the means through the projection's ``v_depth`` (:func:`expected_depth`)."""
+    whose gradient reaches the means through the projection's ``v_depth`` (:func:`expected_depth`).
+    ``absgrad=True`` raises ``ValueError``: the feature walks do not sum absolute gradients (the statistic belongs to
+    the colour pass, ``rasterize_gaussians_fused(absgrad=True)``)."""
+    if absgrad:
+        raise ValueError("absgrad is not supported for feature passes (it belongs to the colour pass: "
+                         "rasterize_gaussians_fused(absgrad=True))")
     if block_width != 16:
         raise ValueError("rasterize_features exists for 16x16 tiles only (block_width=16)")
     if xys.ndimension() != 2 or xys.size(1) != 2:

@@ -446,7 +446,8 @@ def antialiased_opacities(opacity_logits: torch.Tensor, compensation: torch.Tens
 
 def rasterize_gaussians_fused(xys, depths, radii, conics, num_tiles_hit, colors, opacity_logits, img_height,
                               img_width, block_width, background=None, return_alpha=False, id_range=None,
-                              depth_channel=False, group_split=None, compensation=None, opacity_is_logit=True):
+                              depth_channel=False, group_split=None, compensation=None, opacity_is_logit=True,
+                              absgrad: bool = False):
     """``rasterize_gaussians(..., torch.sigmoid(opacity_logits), ...)`` with the sigmoid (and its backward)
     folded into the record build / gradient unpack kernels.
 
@@ -472,7 +473,16 @@ def rasterize_gaussians_fused(xys, depths, radii, conics, num_tiles_hit, colors,
     ``background_acc`` / ``object_acc`` (``sgn_splatfacto_scene_graph.py:364-366``) — accumulated by the SAME walk
     (``sgn_raster_fwd_groups``: each entry belongs to one group and its alpha is evaluated once); each of the two that
     reaches the loss costs one alpha-only reverse walk in the backward.  Kernel options the combined walk does not
-    cover fall back to the three calls."""
+    cover fall back to the three calls.
+
+    ``absgrad=True`` (AbsGS; gsplat's ``absgrad=True``): after ``backward()`` the ``xys`` tensor passed here carries
+    ``xys.absgrad`` [N,2] float32 — per Gaussian the sum over pixels of the ABSOLUTE per-pixel screen-space gradient,
+    where ``xys.grad`` is the signed sum (``sgn_raster_bwd_abs``, ``csrc/raster_absgrad.hip``).  Assigned by every
+    backward, never accumulated; zero for rows nothing touched, all zeros when nothing is visible.  Only the MAIN walk
+    contributes: the accumulation walks of ``group_split`` add to the signed gradients alone.  Whole-scene passes only
+    (``id_range`` raises ``ValueError``); the node's backward then runs call by call."""
+    if absgrad and id_range is not None:
+        raise ValueError("absgrad is not supported for id_range / window passes (whole-scene passes only)")
     assert block_width > 1 and block_width <= 16, "block_width must be between 2 and 16"
     if background is None:
         background = torch.ones(3, dtype=torch.float32, device=colors.device)
@@ -484,6 +494,18 @@ def rasterize_gaussians_fused(xys, depths, radii, conics, num_tiles_hit, colors,
     args = (xys.contiguous(), depths.contiguous(), radii.contiguous(), conics.contiguous(), num_tiles_hit.contiguous(),
             colors.contiguous(), opacity_logits.contiguous(), img_height, img_width, block_width, background.contiguous())
     _ops._call_state.grad = torch.is_grad_enabled()
+
+    def main_pass(*a):
+        # the main pass of this call: with `absgrad`, its node is told whose `.absgrad` to assign (the forward takes the
+        # reference out of the call state; the `finally` covers a call that fails before it gets there)
+        if not (absgrad and torch.is_grad_enabled()):
+            return _RasterizeGaussians.apply(*a)
+        _ops._call_state.absgrad = xys
+        try:
+            return _RasterizeGaussians.apply(*a)
+        finally:
+            _ops._call_state.absgrad = None
+
     if group_split is not None:
         assert id_range is None, "group_split splits the whole scene"
         ro, n = L.opts(), xys.shape[0]
@@ -492,20 +514,20 @@ def rasterize_gaussians_fused(xys, depths, radii, conics, num_tiles_hit, colors,
             # one group is empty (a frame without a visible object): the other one's pass IS the main pass — its
             # accumulation is the alpha image itself, the empty group's is zero.  (Carried through the group kernel, the
             # empty group would never finish and keep every tile's walk alive to the end of its list.)
-            main = _RasterizeGaussians.apply(*args, True, logit, None, bool(depth_channel))
+            main = main_pass(*args, True, logit, None, bool(depth_channel))
             zero = torch.zeros(img_height, img_width, dtype=torch.float32, device=xys.device)
             accs = (zero, main[1]) if s == 0 else (main[1], zero)
             return main[0], main[1], (main[2] if depth_channel else None), accs[0], accs[1]
         if group_accumulation_enabled and block_width == 16:
-            out = _RasterizeGaussians.apply(*args, True, logit, None, bool(depth_channel), False, None, s)
+            out = main_pass(*args, True, logit, None, bool(depth_channel), False, None, s)
             # (the drop-in surface's own policy — option depth_channel=on — may have accumulated the channel unasked)
             return out[0], out[1], (out[2] if depth_channel else None), out[3], out[4]
-        main = _RasterizeGaussians.apply(*args, True, logit, None, bool(depth_channel))
+        main = main_pass(*args, True, logit, None, bool(depth_channel))
         accs = [_RasterizeGaussians.apply(*args, True, logit, (lo, hi), False)[1] if hi > lo
                 else torch.zeros(img_height, img_width, dtype=torch.float32, device=xys.device)
                 for lo, hi in ((0, s), (s, n))]
         return main[0], main[1], (main[2] if depth_channel else None), accs[0], accs[1]
-    return _RasterizeGaussians.apply(*args, return_alpha, logit, id_range, bool(depth_channel))
+    return main_pass(*args, return_alpha, logit, id_range, bool(depth_channel))
 
 
 from . import config as _config

@@ -1835,6 +1835,9 @@ class _RasterizeGaussians(Function):
                                          (opacity if not opacity_logits else None))
         ctx.alpha_clamp_bwd = semantics().alpha_clamp_bwd      # the backward runs with the CALL's value
         ctx.set_materialize_grads(False)       # an unused alpha / depth output arrives as None, not as a zero image
+        # absgrad (fused.rasterize_gaussians_fused(absgrad=True)): the caller's xys tensor, which this node's backward
+        # hands `.absgrad` [N,2] — taken from the call state once, so that no later call inherits it
+        ctx.absgrad_to, _call_state.absgrad = getattr(_call_state, "absgrad", None), None
         # 1. the per-call record: contiguous inputs, options, outputs, binning key (all before any host sync)
         call = _RasterCall(xys, depths, radii, conics, num_tiles_hit, colors, opacity, img_height, img_width, block_width,
                            background, opacity_is_logit, opacity_logits)
@@ -1843,7 +1846,7 @@ class _RasterizeGaussians(Function):
         hit = call.hit = binning_cache_enabled and S.has_binning(key)
         # 2. a sub-model's copy of a window of the cached scene?  (drop-in scene-graph path; see _match_window)
         win = res = None
-        if id_range is None and not hit and S.bin_pending["key"] != key and not want_depth:
+        if id_range is None and not hit and S.bin_pending["key"] != key and not want_depth and ctx.absgrad_to is None:
             # (an explicit depth request is never served as a window of another scene: the window's tensors are
             # window-local, the channel's depths would be read at full-scene ids — it is binned as a scene of its own)
             cand = None
@@ -1978,9 +1981,11 @@ class _RasterizeGaussians(Function):
         v_out_img = None if v_out_img is None else _f32c(v_out_img)
         v_out_alpha = _f32c(v_out_alpha)
 
-        def one_pass(ids, bins, Ts, idx, kmax, v_img, v_alpha, id_range, window, recs, pre, out=None, part=None):
+        def one_pass(ids, bins, Ts, idx, kmax, v_img, v_alpha, id_range, window, recs, pre, out=None, part=None,
+                     v_abs=None):
             # `out` / `part`: one walk of a sequence that accumulates into one gradient workspace (sgn_raster_bwd_part):
             # out = (v_xy, v_conic, v_colors, v_opacity, workspace) shared by the sequence, part = (first, last)
+            # `v_abs` [n,2]: this walk also sums the absolute screen-space gradients (sgn_raster_bwd_abs; call by call)
             lib = L.load()
             if out is None:
                 out = (torch.empty(n, 2, **f32), torch.empty(n, 3, **f32), torch.empty(n, 3, **f32),
@@ -1999,13 +2004,14 @@ class _RasterizeGaussians(Function):
             # for the head / tail groups — so the small-splat classification, which reads that count, stays off for it)
             pairs_known = kmax is ctx.tile_kmax
             S, n_tiles = _S(), bins.shape[0]
-            if composite_backward:
+            one_call = composite_backward and v_abs is None
+            if one_call:
                 order = torch.empty(n_tiles + 2, dtype=torch.int32, device=dev) if tile_order_enabled else None
             else:
                 order = _tile_order(bins, kmax, ctx.ro.adapt_bwd, pairs_known=pairs_known)
             if order is not None and not window and id_range == (0, n):
                 S.walk_stat = order[-1:]             # rides to the host with the next binning's count (mask policy)
-            if composite_backward:
+            if one_call:
                 # ONE library call: launch order + reverse walks + unpack (sgn_rasterize_bwd_all, round 6)
                 scratch = _order_scratch(S, lib, n_tiles, dev) if order is not None else None
                 first, last = (1, 1) if part is None else (int(part[0]), int(part[1]))
@@ -2029,12 +2035,25 @@ class _RasterizeGaussians(Function):
                     L.ptr(v_conic), L.ptr(v_colors), L.ptr(v_opacity), L.ptr(recs), recs.numel(), packed,
                     L.ptr(gws), gws.numel(), L.ptr(order), L.ptr(pre), ro_ptr, L.stream_ptr(),
                     L.aux_stream_ptr(dev) if concurrent_backward else None)
-            if part is None:
+            if v_abs is not None:
+                first, last = (1, 1) if part is None else (int(part[0]), int(part[1]))
+                L.check(lib.sgn_raster_bwd_abs(*args, first, last, L.ptr(v_abs)), "sgn_raster_bwd_abs")
+            elif part is None:
                 L.check(lib.sgn_raster_bwd(*args), "sgn_raster_bwd")
             else:
                 L.check(lib.sgn_raster_bwd_part(*args, int(part[0]), int(part[1])), "sgn_raster_bwd_part")
             return out
 
+        absgrad_to = getattr(ctx, "absgrad_to", None)
+        v_abs = None
+        if absgrad_to is not None:
+            # assigned per backward, never accumulated; zero where the main walk touched nothing (or did not run)
+            assert not ctx.window and ctx.id_range == (0, n), "absgrad: whole-scene passes only"
+            runs = ctx.num_intersects >= 1 and main
+            v_abs = torch.empty(n, 2, **f32) if runs else torch.zeros(n, 2, **f32)
+            absgrad_to.absgrad = v_abs
+            if not runs:
+                v_abs = None
         if ctx.num_intersects < 1 or not (main or group_work):
             v_xy, v_conic = torch.zeros(n, 2, **f32), torch.zeros(n, 3, **f32)
             v_colors, v_opacity = torch.zeros(n, 3, **f32), torch.zeros(n, **f32)
@@ -2053,9 +2072,15 @@ class _RasterizeGaussians(Function):
                 group_stats["backward_passes"] += 1
                 walks.append((g["ids"], g["bins"], g["T"], g["idx"], g["kmax"], None, _f32c(v), (g["lo"], g["hi"]), 0,
                               ctx.recs if g["own"] else None, colors_pre if main else None))
+            if v_abs is not None:
+                # only the MAIN walk sums absolute gradients, and the walk that unpacks them must be the one issued
+                # through sgn_raster_bwd_abs: the main walk goes last (the sums are float atomics: no order to keep)
+                walks = walks[1:] + walks[:1]
             out = None
             for wi, w in enumerate(walks):
-                out = one_pass(*w, out=out, part=None if len(walks) == 1 else (wi == 0, wi == len(walks) - 1))
+                last = wi == len(walks) - 1
+                out = one_pass(*w, out=out, part=None if len(walks) == 1 else (wi == 0, last),
+                               v_abs=v_abs if last else None)
             v_xy, v_conic, v_colors, v_opacity = out[:4]
         v_opacity = v_opacity.reshape(ctx.opacity_shape)
         if no_color_grad:

@@ -134,14 +134,18 @@ def render_fused(P: Dict[str, torch.Tensor], cam: Camera, sh_degree_to_use: int 
                  background: Optional[torch.Tensor] = None, with_depth: bool = False,
                  object_ids: Optional[torch.Tensor] = None, poses: Optional[torch.Tensor] = None,
                  idft: Optional[torch.Tensor] = None, depth_channel: bool = True,
-                 group_split: Optional[int] = None, rasterize_mode: str = "classic") -> SimpleNamespace:
+                 group_split: Optional[int] = None, rasterize_mode: str = "classic",
+                 absgrad: bool = False) -> SimpleNamespace:
     """Same result as :func:`render` on the scene-graph-aggregated parameters, through the fused front
     ends (:mod:`sgn_rast.fused`): raw parameters in, no activation / concat / transform kernels.
     ``P["means"]`` / ``P["quats"]`` are in each object's LOCAL frame when ``object_ids``/``poses`` are given;
     ``P["features_dc"]`` is [N,F,3] with F Fourier coefficients weighted by ``idft[object]``.
     ``rasterize_mode="antialiased"``: ``fused.antialiased_opacities(logits, compensation)`` is formed once and every
     pass takes that one tensor as probabilities; ``out.opacities`` holds it (what a caller's further passes over the
-    same render — ``features.rasterize_features``, ``expected_depth`` — take with ``opacity_is_logit=False``)."""
+    same render — ``features.rasterize_features``, ``expected_depth`` — take with ``opacity_is_logit=False``).
+    ``absgrad=True``: the COLOUR pass also sums the absolute screen-space gradients — ``out.xys.absgrad`` [N,2] after
+    ``backward()`` (:func:`sgn_rast.fused.rasterize_gaussians_fused`); the separate depth pass of
+    ``depth_channel=False`` does not take part."""
     from . import fused
     antialiased = antialiased_mode(rasterize_mode)
     dev = P["means"].device
@@ -173,17 +177,18 @@ def render_fused(P: Dict[str, torch.Tensor], cam: Camera, sh_degree_to_use: int 
             rgb, alpha, depth_im, out.acc_head, out.acc_tail = fused.rasterize_gaussians_fused(
                 xys, depths, radii, conics, num_tiles_hit, rgbs, opac, H, W, block_width,
                 background=background, return_alpha=True, depth_channel=True, group_split=group_split,
-                opacity_is_logit=logit)
+                opacity_is_logit=logit, absgrad=absgrad)
         else:
             rgb, alpha, depth_im = fused.rasterize_gaussians_fused(
                 xys, depths, radii, conics, num_tiles_hit, rgbs, opac, H, W, block_width,
-                background=background, return_alpha=True, depth_channel=True, opacity_is_logit=logit)
+                background=background, return_alpha=True, depth_channel=True, opacity_is_logit=logit,
+                absgrad=absgrad)
         out.rgb, out.alpha, out.rgbs = rgb, alpha, rgbs
         out.depth = torch.where(alpha[..., None] > 1e-3, depth_im[..., None] / alpha[..., None], 10)   # :995
         return out
     rgb, alpha = fused.rasterize_gaussians_fused(xys, depths, radii, conics, num_tiles_hit, rgbs, opac, H, W,
                                                  block_width, background=background, return_alpha=True,
-                                                 opacity_is_logit=logit)
+                                                 opacity_is_logit=logit, absgrad=absgrad)
     out.rgb, out.alpha, out.rgbs = rgb, alpha, rgbs
     if with_depth:
         depth_im = fused.rasterize_gaussians_fused(
@@ -292,15 +297,21 @@ def _submodel_raster(models, world_means, dcs, out, sub, cam: Camera, sh_degree_
 def render_scene_graph(models, poses: torch.Tensor, idft: torch.Tensor, cam: Camera, sh_degree_to_use: int = 3,
                        block_width: int = 16, ops=_hip_ops, fused: bool = False,
                        caller_syncs: bool = True, sh_parts: bool = True, groups: bool = True,
-                       rasterize_mode: str = "classic") -> SimpleNamespace:
+                       rasterize_mode: str = "classic", absgrad: bool = False) -> SimpleNamespace:
     """Replay of ``SplatfactoSceneGraphModel.get_outputs`` in training mode
     (``sgn_splatfacto_scene_graph.py:305-366``): ``models[0]`` is the background, ``models[i>0]`` rigid objects
     whose parameters live in the object's local frame; ``poses[i]`` = [R(9) t(3) q_o2w(4)], ``idft[i]`` = Fourier
     weights of the frame.  Four raster passes like the reference: rgb+alpha, depth, objects-only accumulation,
     background-only accumulation.  ``fused=True`` runs the main pass through :mod:`sgn_rast.fused` (no transform /
     activation / concat kernels) and skips the SH evaluation whose result the reference throws away in the two
-    accumulation passes (``:285``).  ``rasterize_mode``: as :func:`render` / :func:`render_fused`, in every pass."""
+    accumulation passes (``:285``).  ``rasterize_mode``: as :func:`render` / :func:`render_fused`, in every pass.
+    ``absgrad=True`` (fused path only; ``ValueError`` otherwise): the main colour pass sums the absolute screen-space
+    gradients (:func:`render_fused`); after ``backward()``, ``out.xys_absgrad_parts()`` returns the per-sub-model
+    slices of ``out.xys.absgrad`` in model order — what each sub-model's ``after_train`` reads under
+    ``DensifyConfig(absgrad=True)``.  The accumulation passes add nothing to it."""
     antialiased = antialiased_mode(rasterize_mode)
+    if absgrad and not fused:
+        raise ValueError("absgrad is not supported on the drop-in operators (gsplat 0.1.x surface): use fused=True")
     dev = models[0]["means"].device
     H, W = cam.height, cam.width
     counts = [m["means"].shape[0] for m in models]
@@ -313,7 +324,9 @@ def render_scene_graph(models, poses: torch.Tensor, idft: torch.Tensor, cam: Cam
         # False keeps the round-3 form, two more id-range passes, for A/B and for the tests
         out = render_fused(P, cam, sh_degree_to_use, block_width, with_depth=True, object_ids=object_ids,
                            poses=poses, idft=idft_p, group_split=counts[0] if groups else None,
-                           rasterize_mode=rasterize_mode)
+                           rasterize_mode=rasterize_mode, absgrad=absgrad)
+        if absgrad:
+            out.xys_absgrad_parts = lambda: torch.split(out.xys.absgrad, counts)
         if groups:
             out.object_acc, out.background_acc = out.acc_tail, out.acc_head                 # :364-366
             return out
@@ -555,7 +568,7 @@ def train_step(P: Dict[str, torch.Tensor], cam: Camera, w_img: torch.Tensor, w_a
                ssim_lambda: float = 0.2, loss_fn=None, caller_syncs: bool = False, zero_grad: bool = True,
                mask: Optional[torch.Tensor] = None, lidar_depth: Optional[torch.Tensor] = None,
                depth_loss_mult: float = 0.1, depth_loss_kind: str = "l1", rasterize_mode: str = "classic",
-               **fused_kw) -> SimpleNamespace:
+               absgrad: bool = False, densifier=None, step: int = 0, **fused_kw) -> SimpleNamespace:
     """One "train-step image": project fwd -> SH fwd -> rasterize(return_alpha) fwd -> scalar loss ->
     full backward to means / log-scales / raw quats / opacity logits / SH coefficients (the metric's definition,
     SURVEY.md §8d: the operator sequence; ``caller_syncs=True`` adds the two host syncs of the reference's own model
@@ -569,8 +582,16 @@ def train_step(P: Dict[str, torch.Tensor], cam: Camera, w_img: torch.Tensor, w_a
     ``depth_loss_mult * lidar.depth_loss(*features.expected_depth(...), lidar_depth, depth_loss_kind, mask)``: the
     expected depth is composited over the list the RGB pass binned (nothing is binned again) and ``out.depth_loss`` holds
     the term's value; an empty view contributes nothing.  ``rasterize_mode="antialiased"`` multiplies the opacities by
-    the projection's compensation factor (:func:`render` / :func:`render_fused`), in the LiDAR term's pass too."""
+    the projection's compensation factor (:func:`render` / :func:`render_fused`), in the LiDAR term's pass too.
+    ``absgrad=True`` (``fused=True`` only; ``ValueError`` otherwise): the colour pass sums the absolute screen-space
+    gradients, ``out.xys.absgrad`` [N,2] after the backward.  ``densifier`` (a :class:`sgn_rast.densify.Densifier`):
+    its ``after_train(step, ...)`` runs behind the backward with this render's ``xys.grad`` — or, under
+    ``DensifyConfig(absgrad=True)``, its ``xys.absgrad`` — radii and image size."""
     antialiased = antialiased_mode(rasterize_mode)
+    if absgrad and not fused:
+        raise ValueError("absgrad is not supported on the drop-in operators (gsplat 0.1.x surface): use fused=True")
+    if densifier is not None and densifier.cfg.absgrad and not absgrad:
+        raise ValueError("DensifyConfig(absgrad=True) reads xys.absgrad: pass absgrad=True")
     if mask is not None:           # host-side errors first: before the render, let alone the loss, launches anything
         if gt is None:
             raise ValueError("mask applies to the photometric loss: pass gt as well")
@@ -593,7 +614,7 @@ def train_step(P: Dict[str, torch.Tensor], cam: Camera, w_img: torch.Tensor, w_a
             sky["base"].grad = None
     if fused:
         out = render_fused(P, cam, sh_degree_to_use, block_width, with_depth=with_depth, rasterize_mode=rasterize_mode,
-                           **fused_kw)
+                           absgrad=absgrad, **fused_kw)
     else:
         out = render(P, cam, sh_degree_to_use, block_width, with_depth=with_depth, ops=ops,
                      caller_syncs=caller_syncs, rasterize_mode=rasterize_mode)
@@ -627,5 +648,9 @@ def train_step(P: Dict[str, torch.Tensor], cam: Camera, w_img: torch.Tensor, w_a
         loss.backward()
     if reducer is not None:
         reducer.finish()
+    if densifier is not None:     # (an empty view: no gradient, no absgrad — after_train counts it as "saw nothing")
+        ran = loss.requires_grad
+        densifier.after_train(step, out.xys.grad if ran else None, out.radii, (cam.height, cam.width),
+                              absgrad=getattr(out.xys, "absgrad", None) if ran else None)
     out.loss = loss.detach()
     return out

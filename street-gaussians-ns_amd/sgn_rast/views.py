@@ -285,14 +285,18 @@ def _check_rasterize_mode(rasterize_mode: str) -> None:
 def render_views(P: Dict[str, torch.Tensor], cams: Sequence[Camera], sh_degree_to_use: int = 3,
                  background: Optional[torch.Tensor] = None, with_depth: bool = False, block_width: int = BLOCK,
                  object_ids=None, poses=None, idft=None, group_split=None, id_range=None,
-                 rasterize_mode: str = "classic") -> SimpleNamespace:
+                 rasterize_mode: str = "classic", absgrad: bool = False) -> SimpleNamespace:
     """Render ``P`` (the raw leaves of :func:`sgn_rast.step.render_fused`: means, log_scales, quats, opacity_logits,
     features_dc [N,1,3], features_rest) from every camera of ``cams`` (1 to 16 :class:`scenes.Camera`, one image size)
     in one batched call.  Returns ``rgb [B,H,W,3]``, ``alpha [B,H,W]``, with ``with_depth`` also ``depth [B,H,W,1]``
     (as ``render_fused``), and the projection's ``xys [B,N,2]`` (gradient retained), ``depths``, ``radii``,
     ``conics``, ``num_tiles_hit`` as ``[B,N,...]`` (per view: feed ``densify.Stats.update`` with ``xys.grad[b]``,
     ``radii[b]``).  View b equals ``render_fused(P, cams[b])`` bit for bit.  ``rasterize_mode``: "classic" only;
-    "antialiased" raises ``NotImplementedError`` (per-view compensation factors, see ``_check_rasterize_mode``)."""
+    "antialiased" raises ``NotImplementedError`` (per-view compensation factors, see ``_check_rasterize_mode``).
+    ``absgrad=True`` raises ``ValueError``: the batched walks do not sum absolute gradients (single views do:
+    ``render_fused(absgrad=True)``)."""
+    if absgrad:
+        raise ValueError("absgrad is not supported for batched views (render each view with render_fused(absgrad=True))")
     _check_rasterize_mode(rasterize_mode)
     b, n, h, w = check_views(P, cams, block_width, object_ids=object_ids, poses=poses, idft=idft,
                              group_split=group_split, id_range=id_range)
