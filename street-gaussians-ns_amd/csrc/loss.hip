@@ -330,99 +330,91 @@ SGN_EXPORT size_t sgn_l1_ssim_workspace_bytes(int h, int w, int with_grad) {
     return partial_bytes(h, w) + (with_grad ? (size_t)9 * (h - HALO) * (w - HALO) * sizeof(float) : 0);
 }
 
-SGN_EXPORT int sgn_l1_ssim_fwd(int h, int w, const float *pred, const float *gt, float data_range, float clamp_max,
-                               float ssim_lambda, float *out3 /*device: [Ll1, ssim, (1-l) Ll1 + l (1-ssim)]*/,
-                               int with_grad, void *ws, size_t ws_bytes, sgn_stream_t stream) {
-    SGN_ARG_CHECK(h > HALO && w > HALO, -1);      // pytorch_msssim asserts the image is larger than the window
-    SGN_ARG_CHECK(pred && gt && out3 && ws, -2);
-    SGN_ARG_CHECK(ws_bytes >= sgn_l1_ssim_workspace_bytes(h, w, with_grad), -3);
-    hipStream_t s = (hipStream_t)stream;
-    float *partials = (float *)ws;
-    float *dmaps = with_grad ? (float *)((char *)ws + partial_bytes(h, w)) : nullptr;
-    const Win win = make_window(1.5f);
-    const float C1 = (0.01f * data_range) * (0.01f * data_range), C2 = (0.03f * data_range) * (0.03f * data_range);
-    const dim3 grid(sgn_cdiv(w, TS), sgn_cdiv(h, TS));
-    sgn_timing_begin(SGN_T_LOSS_FWD, (void *)s);
-    hipLaunchKernelGGL((l1_ssim_fwd_kernel<false, false>), grid, dim3(256), 0, s, h, w, win, C1, C2, clamp_max, pred, gt,
-                       partials, dmaps, (const unsigned char *)nullptr);
-    hipLaunchKernelGGL(l1_ssim_reduce_kernel<false>, dim3(1), dim3(256), 0, s, (int)(grid.x * grid.y), partials,
-                       1.f / (3.f * (float)h * (float)w), 1.f / (3.f * (float)(h - HALO) * (float)(w - HALO)),
-                       ssim_lambda, out3);
-    sgn_timing_end(SGN_T_LOSS_FWD, (void *)s);
-    SGN_LAUNCH_CHECK();
-    return 0;
-}
-
-SGN_EXPORT int sgn_l1_ssim_bwd(int h, int w, const float *pred, const float *gt, float clamp_max, const void *ws,
-                               const float *gscale2 /*device: [d loss/d Ll1, d loss/d ssim]*/, float *v_pred,
-                               sgn_stream_t stream) {
-    SGN_ARG_CHECK(h > HALO && w > HALO, -1);
-    SGN_ARG_CHECK(pred && gt && ws && gscale2 && v_pred, -2);
-    hipStream_t s = (hipStream_t)stream;
-    const float *dmaps = (const float *)((const char *)ws + partial_bytes(h, w));
-    const Win win = make_window(1.5f);
-    sgn_timing_begin(SGN_T_LOSS_BWD, (void *)s);
-    hipLaunchKernelGGL(l1_ssim_bwd_kernel<false>, dim3(sgn_cdiv(w, TS), sgn_cdiv(h, TS)), dim3(256), 0, s, h, w, win,
-                       clamp_max, pred, gt, dmaps, gscale2, v_pred, (const unsigned char *)nullptr);
-    sgn_timing_end(SGN_T_LOSS_BWD, (void *)s);
-    SGN_LAUNCH_CHECK();
-    return 0;
-}
-
-// The masked entry points (mask == NULL: no mask, still with the MSE slot).  Their workspace differs from the unmasked
-// one only in the partials' stride: [3 floats per workgroup][the same 9 maps].
+// The masked and byte entry points' workspace differs from the unmasked one only in the partials' stride: [3 floats per
+// workgroup][the same 9 maps].
 SGN_EXPORT size_t sgn_l1_ssim_masked_workspace_bytes(int h, int w, int with_grad) {
     if (h <= HALO || w <= HALO) return 256;
     return partial_bytes(h, w, 3) + (with_grad ? (size_t)9 * (h - HALO) * (w - HALO) * sizeof(float) : 0);
 }
 
-SGN_EXPORT int sgn_l1_ssim_masked_fwd(int h, int w, const float *pred, const float *gt, const unsigned char *mask,
-                                      float data_range, float clamp_max, float ssim_lambda,
-                                      float *out4 /*device: [Ll1, ssim, (1-l) Ll1 + l (1-ssim), mse]*/, int with_grad,
-                                      void *ws, size_t ws_bytes, sgn_stream_t stream) {
-    SGN_ARG_CHECK(h > HALO && w > HALO, -1);
-    SGN_ARG_CHECK(pred && gt && out4 && ws, -2);
-    SGN_ARG_CHECK(ws_bytes >= sgn_l1_ssim_masked_workspace_bytes(h, w, with_grad), -3);
+// The forward of all three entry pairs, reported under the entry's name `fn`.  MSE: the entry has the fourth output and
+// three partial sums per workgroup (else two, and no mask).  `out`, device: [Ll1, ssim, (1-l) Ll1 + l (1-ssim)(, mse)].
+template <typename GT, bool MSE>
+static int l1_ssim_fwd_launch(const char *fn, int h, int w, const float *pred, const GT *gt, const unsigned char *mask,
+                              float data_range, float clamp_max, float ssim_lambda, float *out, int with_grad, void *ws,
+                              size_t ws_bytes, sgn_stream_t stream) {
+    SGN_ARG_CHECK_FN(fn, h > HALO && w > HALO, -1);   // pytorch_msssim asserts the image is larger than the window
+    SGN_ARG_CHECK_FN(fn, pred && gt && out && ws, -2);
+    const auto workspace_bytes = MSE ? sgn_l1_ssim_masked_workspace_bytes : sgn_l1_ssim_workspace_bytes;
+    SGN_ARG_CHECK_FN(fn, ws_bytes >= workspace_bytes(h, w, with_grad), -3);
     hipStream_t s = (hipStream_t)stream;
     float *partials = (float *)ws;
-    float *dmaps = with_grad ? (float *)((char *)ws + partial_bytes(h, w, 3)) : nullptr;
+    float *dmaps = with_grad ? (float *)((char *)ws + partial_bytes(h, w, MSE ? 3 : 2)) : nullptr;
     const Win win = make_window(1.5f);
     const float C1 = (0.01f * data_range) * (0.01f * data_range), C2 = (0.03f * data_range) * (0.03f * data_range);
     const dim3 grid(sgn_cdiv(w, TS), sgn_cdiv(h, TS));
     sgn_timing_begin(SGN_T_LOSS_FWD, (void *)s);
-    if (mask)
-        hipLaunchKernelGGL((l1_ssim_fwd_kernel<true, true>), grid, dim3(256), 0, s, h, w, win, C1, C2, clamp_max, pred,
+    if (MSE && mask)
+        hipLaunchKernelGGL((l1_ssim_fwd_kernel<MSE, MSE, GT>), grid, dim3(256), 0, s, h, w, win, C1, C2, clamp_max, pred,
                            gt, partials, dmaps, mask);
     else
-        hipLaunchKernelGGL((l1_ssim_fwd_kernel<false, true>), grid, dim3(256), 0, s, h, w, win, C1, C2, clamp_max, pred,
+        hipLaunchKernelGGL((l1_ssim_fwd_kernel<false, MSE, GT>), grid, dim3(256), 0, s, h, w, win, C1, C2, clamp_max, pred,
                            gt, partials, dmaps, mask);
-    hipLaunchKernelGGL(l1_ssim_reduce_kernel<true>, dim3(1), dim3(256), 0, s, (int)(grid.x * grid.y), partials,
+    hipLaunchKernelGGL(l1_ssim_reduce_kernel<MSE>, dim3(1), dim3(256), 0, s, (int)(grid.x * grid.y), partials,
                        1.f / (3.f * (float)h * (float)w), 1.f / (3.f * (float)(h - HALO) * (float)(w - HALO)),
-                       ssim_lambda, out4);
+                       ssim_lambda, out);
     sgn_timing_end(SGN_T_LOSS_FWD, (void *)s);
     SGN_LAUNCH_CHECK();
     return 0;
 }
 
-SGN_EXPORT int sgn_l1_ssim_masked_bwd(int h, int w, const float *pred, const float *gt, const unsigned char *mask,
-                                      float clamp_max, const void *ws, const float *gscale2, float *v_pred,
-                                      sgn_stream_t stream) {
-    SGN_ARG_CHECK(h > HALO && w > HALO, -1);
-    SGN_ARG_CHECK(pred && gt && ws && gscale2 && v_pred, -2);
+// The backward likewise; gscale2: [d loss/d Ll1, d loss/d ssim] on the device.
+template <typename GT, bool MSE>
+static int l1_ssim_bwd_launch(const char *fn, int h, int w, const float *pred, const GT *gt, const unsigned char *mask,
+                              float clamp_max, const void *ws, const float *gscale2, float *v_pred, sgn_stream_t stream) {
+    SGN_ARG_CHECK_FN(fn, h > HALO && w > HALO, -1);
+    SGN_ARG_CHECK_FN(fn, pred && gt && ws && gscale2 && v_pred, -2);
     hipStream_t s = (hipStream_t)stream;
-    const float *dmaps = (const float *)((const char *)ws + partial_bytes(h, w, 3));
+    const float *dmaps = (const float *)((const char *)ws + partial_bytes(h, w, MSE ? 3 : 2));
     const Win win = make_window(1.5f);
     const dim3 grid(sgn_cdiv(w, TS), sgn_cdiv(h, TS));
     sgn_timing_begin(SGN_T_LOSS_BWD, (void *)s);
     if (mask)
-        hipLaunchKernelGGL(l1_ssim_bwd_kernel<true>, grid, dim3(256), 0, s, h, w, win, clamp_max, pred, gt, dmaps, gscale2,
-                           v_pred, mask);
+        hipLaunchKernelGGL((l1_ssim_bwd_kernel<true, GT>), grid, dim3(256), 0, s, h, w, win, clamp_max, pred, gt, dmaps,
+                           gscale2, v_pred, mask);
     else
-        hipLaunchKernelGGL(l1_ssim_bwd_kernel<false>, grid, dim3(256), 0, s, h, w, win, clamp_max, pred, gt, dmaps, gscale2,
-                           v_pred, mask);
+        hipLaunchKernelGGL((l1_ssim_bwd_kernel<false, GT>), grid, dim3(256), 0, s, h, w, win, clamp_max, pred, gt, dmaps,
+                           gscale2, v_pred, mask);
     sgn_timing_end(SGN_T_LOSS_BWD, (void *)s);
     SGN_LAUNCH_CHECK();
     return 0;
+}
+
+SGN_EXPORT int sgn_l1_ssim_fwd(int h, int w, const float *pred, const float *gt, float data_range, float clamp_max,
+                               float ssim_lambda, float *out3, int with_grad, void *ws, size_t ws_bytes,
+                               sgn_stream_t stream) {
+    return l1_ssim_fwd_launch<float, false>(__func__, h, w, pred, gt, nullptr, data_range, clamp_max, ssim_lambda, out3,
+                                            with_grad, ws, ws_bytes, stream);
+}
+
+SGN_EXPORT int sgn_l1_ssim_bwd(int h, int w, const float *pred, const float *gt, float clamp_max, const void *ws,
+                               const float *gscale2, float *v_pred, sgn_stream_t stream) {
+    return l1_ssim_bwd_launch<float, false>(__func__, h, w, pred, gt, nullptr, clamp_max, ws, gscale2, v_pred, stream);
+}
+
+// The masked entry points (mask == NULL: no mask, still with the MSE slot).
+SGN_EXPORT int sgn_l1_ssim_masked_fwd(int h, int w, const float *pred, const float *gt, const unsigned char *mask,
+                                      float data_range, float clamp_max, float ssim_lambda,
+                                      float *out4 /*device: [Ll1, ssim, (1-l) Ll1 + l (1-ssim), mse]*/, int with_grad,
+                                      void *ws, size_t ws_bytes, sgn_stream_t stream) {
+    return l1_ssim_fwd_launch<float, true>(__func__, h, w, pred, gt, mask, data_range, clamp_max, ssim_lambda, out4,
+                                           with_grad, ws, ws_bytes, stream);
+}
+
+SGN_EXPORT int sgn_l1_ssim_masked_bwd(int h, int w, const float *pred, const float *gt, const unsigned char *mask,
+                                      float clamp_max, const void *ws, const float *gscale2, float *v_pred,
+                                      sgn_stream_t stream) {
+    return l1_ssim_bwd_launch<float, true>(__func__, h, w, pred, gt, mask, clamp_max, ws, gscale2, v_pred, stream);
 }
 
 // The byte-ground-truth entry points: the masked ones with gt as the uint8 [h,w,3] image (mask == NULL: no mask), the
@@ -431,49 +423,15 @@ SGN_EXPORT int sgn_l1_ssim_gt8_fwd(int h, int w, const float *pred, const unsign
                                    float data_range, float clamp_max, float ssim_lambda,
                                    float *out4 /*device: [Ll1, ssim, (1-l) Ll1 + l (1-ssim), mse]*/, int with_grad,
                                    void *ws, size_t ws_bytes, sgn_stream_t stream) {
-    SGN_ARG_CHECK(h > HALO && w > HALO, -1);
-    SGN_ARG_CHECK(pred && gt && out4 && ws, -2);
-    SGN_ARG_CHECK(ws_bytes >= sgn_l1_ssim_masked_workspace_bytes(h, w, with_grad), -3);
-    hipStream_t s = (hipStream_t)stream;
-    float *partials = (float *)ws;
-    float *dmaps = with_grad ? (float *)((char *)ws + partial_bytes(h, w, 3)) : nullptr;
-    const Win win = make_window(1.5f);
-    const float C1 = (0.01f * data_range) * (0.01f * data_range), C2 = (0.03f * data_range) * (0.03f * data_range);
-    const dim3 grid(sgn_cdiv(w, TS), sgn_cdiv(h, TS));
-    sgn_timing_begin(SGN_T_LOSS_FWD, (void *)s);
-    if (mask)
-        hipLaunchKernelGGL((l1_ssim_fwd_kernel<true, true, unsigned char>), grid, dim3(256), 0, s, h, w, win, C1, C2,
-                           clamp_max, pred, gt, partials, dmaps, mask);
-    else
-        hipLaunchKernelGGL((l1_ssim_fwd_kernel<false, true, unsigned char>), grid, dim3(256), 0, s, h, w, win, C1, C2,
-                           clamp_max, pred, gt, partials, dmaps, mask);
-    hipLaunchKernelGGL(l1_ssim_reduce_kernel<true>, dim3(1), dim3(256), 0, s, (int)(grid.x * grid.y), partials,
-                       1.f / (3.f * (float)h * (float)w), 1.f / (3.f * (float)(h - HALO) * (float)(w - HALO)),
-                       ssim_lambda, out4);
-    sgn_timing_end(SGN_T_LOSS_FWD, (void *)s);
-    SGN_LAUNCH_CHECK();
-    return 0;
+    return l1_ssim_fwd_launch<unsigned char, true>(__func__, h, w, pred, gt, mask, data_range, clamp_max, ssim_lambda,
+                                                   out4, with_grad, ws, ws_bytes, stream);
 }
 
 SGN_EXPORT int sgn_l1_ssim_gt8_bwd(int h, int w, const float *pred, const unsigned char *gt, const unsigned char *mask,
                                    float clamp_max, const void *ws, const float *gscale2, float *v_pred,
                                    sgn_stream_t stream) {
-    SGN_ARG_CHECK(h > HALO && w > HALO, -1);
-    SGN_ARG_CHECK(pred && gt && ws && gscale2 && v_pred, -2);
-    hipStream_t s = (hipStream_t)stream;
-    const float *dmaps = (const float *)((const char *)ws + partial_bytes(h, w, 3));
-    const Win win = make_window(1.5f);
-    const dim3 grid(sgn_cdiv(w, TS), sgn_cdiv(h, TS));
-    sgn_timing_begin(SGN_T_LOSS_BWD, (void *)s);
-    if (mask)
-        hipLaunchKernelGGL((l1_ssim_bwd_kernel<true, unsigned char>), grid, dim3(256), 0, s, h, w, win, clamp_max, pred, gt,
-                           dmaps, gscale2, v_pred, mask);
-    else
-        hipLaunchKernelGGL((l1_ssim_bwd_kernel<false, unsigned char>), grid, dim3(256), 0, s, h, w, win, clamp_max, pred,
-                           gt, dmaps, gscale2, v_pred, mask);
-    sgn_timing_end(SGN_T_LOSS_BWD, (void *)s);
-    SGN_LAUNCH_CHECK();
-    return 0;
+    return l1_ssim_bwd_launch<unsigned char, true>(__func__, h, w, pred, gt, mask, clamp_max, ws, gscale2, v_pred,
+                                                   stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

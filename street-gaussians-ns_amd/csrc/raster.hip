@@ -918,6 +918,21 @@ __global__ __launch_bounds__(256) void unpack_views_kernel(int n, int n_views, c
     v_opac[i] = vsum;
 }
 
+// this unit's backward families for sgn_raster_bwd_launch (raster_common.h), [exact_exp][reduce_mode]
+const RasterBwdFamily bwd_family = {
+    {{raster_bwd_kernel<false, 0, 4, true, 0>, raster_bwd_kernel<false, 1, 4, true, 0>},
+     {raster_bwd_kernel<true, 0, 4, true, 0>, raster_bwd_kernel<true, 1, 4, true, 0>}},
+    {{raster_bwd_kernel<false, 0, 1, false, 2>, raster_bwd_kernel<false, 1, 1, false, 2>},
+     {raster_bwd_kernel<true, 0, 1, false, 2>, raster_bwd_kernel<true, 1, 1, false, 2>}},
+    {{raster_bwd_short_kernel<false, 0>, raster_bwd_short_kernel<false, 1>},
+     {raster_bwd_short_kernel<true, 0>, raster_bwd_short_kernel<true, 1>}}};
+const RasterBwdFamily views_bwd_family = {   // always the two-kernel scheme
+    {},
+    {{raster_views_bwd_kernel<false, 0>, raster_views_bwd_kernel<false, 1>},
+     {raster_views_bwd_kernel<true, 0>, raster_views_bwd_kernel<true, 1>}},
+    {{raster_views_bwd_short_kernel<false, 0>, raster_views_bwd_short_kernel<false, 1>},
+     {raster_views_bwd_short_kernel<true, 0>, raster_views_bwd_short_kernel<true, 1>}}};
+
 }  // namespace
 
 SGN_EXPORT void sgn_raster_default_opts(sgn_raster_opts *out) {
@@ -1170,85 +1185,87 @@ SGN_EXPORT int sgn_depth_reuse(int img_h, int img_w, const int32_t *flag, const 
     return 0;
 }
 
-static int raster_bwd_impl(int img_h, int img_w, int block_width, int n, int64_t n_isect,
-                              const int32_t *gaussian_ids_sorted, const int32_t *tile_bins, const float *xys,
-                              const float *conics, const float *colors, const float *opacities,
-                              int opacity_is_logit, int id_lo, int id_hi, int window, const float *background3,
-                              const float *final_Ts, const int32_t *final_idx,
-                              const float *v_out_img, const float *v_out_alpha, float alpha_clamp_bwd,
-                              float *v_xy, float *v_conic, float *v_colors, float *v_opacity, void *recs_ws,
-                              size_t recs_ws_bytes, int recs_packed, void *grad_ws, size_t grad_ws_bytes,
-                              const int32_t *tile_order, const float *colors_pre_clamp,
-                              const sgn_raster_opts *opts, sgn_stream_t stream, sgn_stream_t aux_stream,
-                              int keep_ws, int defer_unpack) {
-    const sgn_raster_opts o = resolve_opts(opts);
-    SGN_ARG_CHECK(opacity_is_logit >= 0 && opacity_is_logit <= 2, -11);
-    const int logit_rows = opacity_is_logit == 1;     // 2: the values ARE probabilities, only the gradient is converted
-    SGN_ARG_CHECK(!window || (0 <= id_lo && id_lo <= id_hi && id_hi <= n), -9);
-    SGN_ARG_CHECK(img_h > 0 && img_w > 0 && n >= 0, -1);
-    SGN_ARG_CHECK(block_width >= 2 && block_width <= 16, -2);
-    SGN_ARG_CHECK(n_isect >= 0 && n_isect < ((int64_t)1 << 31), -3);
-    if (n == 0) return 0;
-    SGN_ARG_CHECK(v_xy && v_conic && v_colors && v_opacity && grad_ws && opacities && conics, -4);
-    SGN_ARG_CHECK(grad_ws_bytes >= sgn_raster_bwd_workspace_bytes(n), -5);
-    SGN_ARG_CHECK(alpha_clamp_bwd > 0.f && alpha_clamp_bwd < 1.f, -6);
-    SGN_ARG_CHECK(!o.ids_qmask || (block_width == 16 && n < SGN_QMASK_MAX_IDS), -10);
-    hipStream_t s = (hipStream_t)stream;
-    if (!keep_ws) SGN_HIP_CHECK(hipMemsetAsync(grad_ws, 0, (size_t)n * SGN_RECORD_FLOATS * sizeof(float), s));
-    if (n_isect > 0) {
-        SGN_ARG_CHECK(gaussian_ids_sorted && tile_bins && xys && conics && colors && opacities && background3 &&
-                          final_Ts && final_idx && v_out_alpha && recs_ws, -7);     // (v_out_img may be NULL: zeros)
-        SGN_ARG_CHECK(recs_ws_bytes >= sgn_raster_workspace_bytes(n, n_isect, &o), -8);
-        if (!recs_packed)
-            pack_records(n, xys, conics, colors, opacities, logit_rows, id_lo, id_hi, window, recs_ws, s);
-        const int tiles_x = (img_w + block_width - 1) / block_width, tiles_y = (img_h + block_width - 1) / block_width;
-        const Rec *rows = (const Rec *)recs_ws;
-        const int n_tiles = tiles_x * tiles_y;
-        const int long_grid = n_tiles * 4;   // the long-walk kernel: workgroups beyond 4 * n_long exit at once
-        // fork: the long-walk kernel goes to the auxiliary stream (if any) behind everything queued so far
-        const bool two_kernel = tile_order != nullptr && block_width == 16;
-        hipStream_t s2 = s;
-        hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-        if (two_kernel && aux_stream != nullptr && (hipStream_t)aux_stream != s && sgn_fork_events(&ev_fork, &ev_join) == 0) {
-            s2 = (hipStream_t)aux_stream;
-            SGN_HIP_CHECK(hipEventRecord(ev_fork, s));
-            SGN_HIP_CHECK(hipStreamWaitEvent(s2, ev_fork, 0));
-        }
-        sgn_timing_begin(SGN_T_RASTER_BWD, s);
-#define SGN_BWD_ARGS                                                                                             \
-    img_w, img_h, block_width, tiles_x, n_tiles, (const int2 *)tile_bins, rows, gaussian_ids_sorted, background3, \
-        final_Ts, final_idx, v_out_img, v_out_alpha, alpha_clamp_bwd, (float *)grad_ws, o.debug_flags, o.adapt_bwd, \
-        o.batch_bwd, tile_order, o.ids_qmask
-#define SGN_LAUNCH_BWD(EX, RM)                                                                                   \
-    do {                                                                                                         \
-        if (!two_kernel)     /* no launch order / tiles other than 16x16: the in-kernel adaptive split */        \
-            hipLaunchKernelGGL((raster_bwd_kernel<EX, RM, 4, true, 0>), dim3(n_tiles * 4), dim3(64), 0, s, SGN_BWD_ARGS); \
-        else {   /* two-kernel adaptive scheme: order[0..n_long) = long walks, the rest short; the two halves */ \
-                 /* touch disjoint tiles and run CONCURRENTLY when the caller lends a second stream           */ \
-            hipLaunchKernelGGL((raster_bwd_kernel<EX, RM, 1, false, 2>), dim3(long_grid), dim3(64), 0, s2, SGN_BWD_ARGS); \
-            hipLaunchKernelGGL((raster_bwd_short_kernel<EX, RM>), dim3(n_tiles), dim3(64), 0, s, SGN_BWD_ARGS);   \
-        }                                                                                                        \
-    } while (0)
-        if (o.exact_exp) {
-            if (o.reduce_mode) SGN_LAUNCH_BWD(true, 1); else SGN_LAUNCH_BWD(true, 0);
-        } else {
-            if (o.reduce_mode) SGN_LAUNCH_BWD(false, 1); else SGN_LAUNCH_BWD(false, 0);
-        }
-#undef SGN_LAUNCH_BWD
-#undef SGN_BWD_ARGS
-        if (s2 != s) {   // join: the unpack (and everything after) waits for the long-walk kernel
-            SGN_HIP_CHECK(hipEventRecord(ev_join, s2));
-            SGN_HIP_CHECK(hipStreamWaitEvent(s, ev_join, 0));
-        }
-        sgn_timing_end(SGN_T_RASTER_BWD, s);
+// The reverse walks of one backward, whichever family (raster_common.h).  The long-walk kernel is queued first — on
+// `aux`, behind everything queued on `s` so far, when the caller lent a second stream — and the short-walk kernel on
+// `s`: the two halves touch disjoint tiles and run CONCURRENTLY then.  Launch errors are left for the caller's check.
+extern "C" int sgn_raster_bwd_launch(const RasterBwdFamily *family, const RasterBwdArgs *a, int two_kernel,
+                                     hipStream_t s, hipStream_t aux) {
+    hipStream_t s2 = s;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    if (two_kernel && aux != nullptr && aux != s && sgn_fork_events(&ev_fork, &ev_join) == 0) {
+        s2 = aux;
+        SGN_HIP_CHECK(hipEventRecord(ev_fork, s));
+        SGN_HIP_CHECK(hipStreamWaitEvent(s2, ev_fork, 0));
     }
+    sgn_timing_begin(SGN_T_RASTER_BWD, s);
+    const int ex = a->o.exact_exp, rm = a->o.reduce_mode;
+    const auto launch = [a](RasterBwdKernel kernel, int grid, hipStream_t on) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), 0, on, a->W, a->H, a->i2, a->i3, a->n_tiles, a->bins, a->recs,
+                           a->ids, a->bg, a->final_T, a->final_idx, a->v_out, a->v_out_alpha, a->alpha_clamp, a->grad_ws,
+                           a->o.debug_flags, a->o.adapt_bwd, a->o.batch_bwd, a->tile_order, a->o.ids_qmask);
+    };
+    if (!two_kernel) {
+        launch(family->adaptive[ex][rm], a->n_tiles * 4, s);
+    } else {   // the long-walk kernel's workgroups beyond 4 * n_long exit at once
+        launch(family->long_walk[ex][rm], a->n_tiles * 4, s2);
+        launch(family->short_walk[ex][rm], a->n_tiles, s);
+    }
+    if (s2 != s) {   // join: the unpack (and everything after) waits for the long-walk kernel
+        SGN_HIP_CHECK(hipEventRecord(ev_join, s2));
+        SGN_HIP_CHECK(hipStreamWaitEvent(s, ev_join, 0));
+    }
+    sgn_timing_end(SGN_T_RASTER_BWD, s);
+    return 0;
+}
+
+extern "C" int sgn_raster_bwd_walks(const char *fn, const RasterBwdFamily *family, const RasterBwdCall *c,
+                                    int clear_ws) {
+    const int n = c->n, block_width = c->block_width, window = c->window, id_lo = c->id_lo, id_hi = c->id_hi;
+    const int64_t n_isect = c->n_isect;
+    const size_t grad_ws_bytes = c->grad_ws_bytes, recs_ws_bytes = c->recs_ws_bytes;
+    const sgn_raster_opts o = resolve_opts(c->opts);
+    SGN_ARG_CHECK_FN(fn, c->opacity_is_logit >= 0 && c->opacity_is_logit <= 2, -11);
+    const int logit_rows = c->opacity_is_logit == 1;  // 2: the values ARE probabilities, only the gradient is converted
+    SGN_ARG_CHECK_FN(fn, !window || (0 <= id_lo && id_lo <= id_hi && id_hi <= n), -9);
+    SGN_ARG_CHECK_FN(fn, c->img_h > 0 && c->img_w > 0 && n >= 0, -1);
+    SGN_ARG_CHECK_FN(fn, block_width >= 2 && block_width <= 16, -2);
+    SGN_ARG_CHECK_FN(fn, n_isect >= 0 && n_isect < ((int64_t)1 << 31), -3);
+    if (n == 0) return 0;
+    SGN_ARG_CHECK_FN(fn, c->v_xy && c->v_conic && c->v_colors && c->v_opacity && c->grad_ws && c->opacities && c->conics,
+                     -4);
+    SGN_ARG_CHECK_FN(fn, grad_ws_bytes >= sgn_raster_bwd_workspace_bytes(n), -5);
+    SGN_ARG_CHECK_FN(fn, c->alpha_clamp_bwd > 0.f && c->alpha_clamp_bwd < 1.f, -6);
+    SGN_ARG_CHECK_FN(fn, !o.ids_qmask || (block_width == 16 && n < SGN_QMASK_MAX_IDS), -10);
+    hipStream_t s = (hipStream_t)c->stream;
+    if (clear_ws) SGN_HIP_CHECK(hipMemsetAsync(c->grad_ws, 0, (size_t)n * SGN_RECORD_FLOATS * sizeof(float), s));
+    if (n_isect == 0) return 0;
+    SGN_ARG_CHECK_FN(fn, c->gaussian_ids_sorted && c->tile_bins && c->xys && c->conics && c->colors && c->opacities &&
+                             c->background3 && c->final_Ts && c->final_idx && c->v_out_alpha && c->recs_ws,
+                     -7);                                                           // (v_out_img may be NULL: zeros)
+    SGN_ARG_CHECK_FN(fn, recs_ws_bytes >= sgn_raster_workspace_bytes(n, n_isect, &o), -8);
+    if (!c->recs_packed)
+        pack_records(n, c->xys, c->conics, c->colors, c->opacities, logit_rows, id_lo, id_hi, window, c->recs_ws, s);
+    const int tiles_x = (c->img_w + block_width - 1) / block_width, tiles_y = (c->img_h + block_width - 1) / block_width;
+    const RasterBwdArgs a = {c->img_w, c->img_h, block_width, tiles_x, tiles_x * tiles_y, (const int2 *)c->tile_bins,
+                             (const Rec *)c->recs_ws, c->gaussian_ids_sorted, c->background3, c->final_Ts, c->final_idx,
+                             c->v_out_img, c->v_out_alpha, c->alpha_clamp_bwd, (float *)c->grad_ws, c->tile_order, o};
+    // the two-kernel scheme needs the launch order and 16x16 tiles; otherwise the in-kernel adaptive split
+    const bool two_kernel = c->tile_order != nullptr && block_width == 16;
+    return sgn_raster_bwd_launch(family, &a, two_kernel, s, (hipStream_t)c->aux_stream);
+}
+
+// sgn_raster_bwd and sgn_raster_bwd_part behind their own checks: the walks, then (last) the unpack
+static int raster_bwd_plain(const char *fn, const RasterBwdCall &c, int first, int last) {
+    const int rc = sgn_raster_bwd_walks(fn, &bwd_family, &c, first);
+    if (rc != 0 || c.n == 0) return rc;
+    hipStream_t s = (hipStream_t)c.stream;
     sgn_timing_begin(SGN_T_UNPACK, s);
-    if (!defer_unpack) {   // window: the outputs (and `opacities`) hold rows [id_lo, id_hi) only
-        const int n_out = window ? id_hi - id_lo : n, row0 = window ? id_lo : 0;
+    if (last) {   // window: the outputs (and `opacities`) hold rows [id_lo, id_hi) only
+        const int n_out = c.window ? c.id_hi - c.id_lo : c.n, row0 = c.window ? c.id_lo : 0;
         if (n_out > 0)
             hipLaunchKernelGGL(unpack_grads_kernel, dim3(sgn_cdiv(n_out, 256)), dim3(256), 0, s, n_out, row0,
-                               (const float *)grad_ws, conics, opacities, opacity_is_logit, colors_pre_clamp, v_xy,
-                               v_conic, v_colors, v_opacity);
+                               (const float *)c.grad_ws, c.conics, c.opacities, c.opacity_is_logit, c.colors_pre_clamp,
+                               c.v_xy, c.v_conic, c.v_colors, c.v_opacity);
     }
     sgn_timing_end(SGN_T_UNPACK, s);
     SGN_LAUNCH_CHECK();
@@ -1265,7 +1282,12 @@ SGN_EXPORT int sgn_raster_bwd(int img_h, int img_w, int block_width, int n, int6
                               size_t recs_ws_bytes, int recs_packed, void *grad_ws, size_t grad_ws_bytes,
                               const int32_t *tile_order, const float *colors_pre_clamp,
                               const sgn_raster_opts *opts, sgn_stream_t stream, sgn_stream_t aux_stream) {
-    return raster_bwd_impl(img_h, img_w, block_width, n, n_isect, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, opacity_is_logit, id_lo, id_hi, window, background3, final_Ts, final_idx, v_out_img, v_out_alpha, alpha_clamp_bwd, v_xy, v_conic, v_colors, v_opacity, recs_ws, recs_ws_bytes, recs_packed, grad_ws, grad_ws_bytes, tile_order, colors_pre_clamp, opts, stream, aux_stream, 0, 0);
+    const RasterBwdCall c = {img_h, img_w, block_width, n, n_isect, gaussian_ids_sorted, tile_bins, xys, conics, colors,
+                             opacities, opacity_is_logit, id_lo, id_hi, window, background3, final_Ts, final_idx,
+                             v_out_img, v_out_alpha, alpha_clamp_bwd, v_xy, v_conic, v_colors, v_opacity, recs_ws,
+                             recs_ws_bytes, recs_packed, grad_ws, grad_ws_bytes, tile_order, colors_pre_clamp, opts,
+                             stream, aux_stream};
+    return raster_bwd_plain(__func__, c, 1, 1);
 }
 
 // One of SEVERAL reverse walks whose gradients belong to the same tensors (the main pass of sgn_raster_fwd_groups and the
@@ -1285,9 +1307,13 @@ SGN_EXPORT int sgn_raster_bwd_part(int img_h, int img_w, int block_width, int n,
                               const sgn_raster_opts *opts, sgn_stream_t stream, sgn_stream_t aux_stream,
                                    int first, int last) {
     SGN_ARG_CHECK(!window, -13);
-    return raster_bwd_impl(img_h, img_w, block_width, n, n_isect, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, opacity_is_logit, id_lo, id_hi, window, background3, final_Ts, final_idx, v_out_img, v_out_alpha, alpha_clamp_bwd, v_xy, v_conic, v_colors, v_opacity, recs_ws, recs_ws_bytes, recs_packed, grad_ws, grad_ws_bytes, tile_order, colors_pre_clamp, opts, stream, aux_stream, first ? 0 : 1, last ? 0 : 1);
+    const RasterBwdCall c = {img_h, img_w, block_width, n, n_isect, gaussian_ids_sorted, tile_bins, xys, conics, colors,
+                             opacities, opacity_is_logit, id_lo, id_hi, window, background3, final_Ts, final_idx,
+                             v_out_img, v_out_alpha, alpha_clamp_bwd, v_xy, v_conic, v_colors, v_opacity, recs_ws,
+                             recs_ws_bytes, recs_packed, grad_ws, grad_ws_bytes, tile_order, colors_pre_clamp, opts,
+                             stream, aux_stream};
+    return raster_bwd_plain(__func__, c, first, last);
 }
-
 
 // ---- batched views: host side of the raster passes (api.cpp sgn_rasterize_views_*_all)
 int sgn_views_repeat(int n, int n_views, const float *src, float *dst, sgn_stream_t stream) {
@@ -1337,35 +1363,11 @@ int sgn_raster_views_bwd(int n_views, int n, int img_h, int img_w, const int32_t
     const int rows_n = n_views * n;
     hipStream_t s = (hipStream_t)stream;
     SGN_HIP_CHECK(hipMemsetAsync(grad_ws, 0, (size_t)rows_n * SGN_RECORD_FLOATS * sizeof(float), s));
-    hipStream_t s2 = s;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    if (aux_stream != nullptr && (hipStream_t)aux_stream != s && sgn_fork_events(&ev_fork, &ev_join) == 0) {
-        s2 = (hipStream_t)aux_stream;
-        SGN_HIP_CHECK(hipEventRecord(ev_fork, s));
-        SGN_HIP_CHECK(hipStreamWaitEvent(s2, ev_fork, 0));
-    }
-    sgn_timing_begin(SGN_T_RASTER_BWD, s);
-#define SGN_VBWD_ARGS                                                                                            \
-    img_w, img_h, tiles_x, tpv, n_tiles, (const int2 *)tile_bins, (const Rec *)rows, ids, background3, final_Ts,  \
-        final_idx, v_out_img, v_out_alpha, alpha_clamp_bwd, (float *)grad_ws, o.debug_flags, o.adapt_bwd,         \
-        o.batch_bwd, tile_order, o.ids_qmask
-#define SGN_LAUNCH_VBWD(EX, RM)                                                                                  \
-    do {                                                                                                         \
-        hipLaunchKernelGGL((raster_views_bwd_kernel<EX, RM>), dim3(n_tiles * 4), dim3(64), 0, s2, SGN_VBWD_ARGS); \
-        hipLaunchKernelGGL((raster_views_bwd_short_kernel<EX, RM>), dim3(n_tiles), dim3(64), 0, s, SGN_VBWD_ARGS); \
-    } while (0)
-    if (o.exact_exp) {
-        if (o.reduce_mode) SGN_LAUNCH_VBWD(true, 1); else SGN_LAUNCH_VBWD(true, 0);
-    } else {
-        if (o.reduce_mode) SGN_LAUNCH_VBWD(false, 1); else SGN_LAUNCH_VBWD(false, 0);
-    }
-#undef SGN_LAUNCH_VBWD
-#undef SGN_VBWD_ARGS
-    if (s2 != s) {
-        SGN_HIP_CHECK(hipEventRecord(ev_join, s2));
-        SGN_HIP_CHECK(hipStreamWaitEvent(s, ev_join, 0));
-    }
-    sgn_timing_end(SGN_T_RASTER_BWD, s);
+    const RasterBwdArgs a = {img_w, img_h, tiles_x, tpv, n_tiles, (const int2 *)tile_bins, (const Rec *)rows, ids,
+                             background3, final_Ts, final_idx, v_out_img, v_out_alpha, alpha_clamp_bwd, (float *)grad_ws,
+                             tile_order, o};
+    const int rc = sgn_raster_bwd_launch(&views_bwd_family, &a, 1, s, (hipStream_t)aux_stream);
+    if (rc != 0) return rc;
     sgn_timing_begin(SGN_T_UNPACK, s);
     hipLaunchKernelGGL(unpack_views_kernel, dim3(sgn_cdiv(n, 256)), dim3(256), 0, s, n, n_views, (const float *)grad_ws,
                        conics, logits, v_xy, v_conic, v_colors, v_opacity);

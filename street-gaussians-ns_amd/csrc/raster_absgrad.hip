@@ -88,6 +88,15 @@ __global__ __launch_bounds__(256) void unpack_grads_abs_kernel(int n, const floa
     v_xy_abs[2 * i + 1] = c.z;
 }
 
+// this unit's backward family for sgn_raster_bwd_launch (raster_common.h), [exact_exp][reduce_mode]
+const RasterBwdFamily absbwd_family = {
+    {{raster_absbwd_kernel<false, 0, 4, true, 0>, raster_absbwd_kernel<false, 1, 4, true, 0>},
+     {raster_absbwd_kernel<true, 0, 4, true, 0>, raster_absbwd_kernel<true, 1, 4, true, 0>}},
+    {{raster_absbwd_kernel<false, 0, 1, false, 2>, raster_absbwd_kernel<false, 1, 1, false, 2>},
+     {raster_absbwd_kernel<true, 0, 1, false, 2>, raster_absbwd_kernel<true, 1, 1, false, 2>}},
+    {{raster_absbwd_short_kernel<false, 0>, raster_absbwd_short_kernel<false, 1>},
+     {raster_absbwd_short_kernel<true, 0>, raster_absbwd_short_kernel<true, 1>}}};
+
 }  // namespace
 
 // sgn_raster_bwd_part with the absgrad statistic (include/sgn_rast.h).
@@ -101,69 +110,20 @@ SGN_EXPORT int sgn_raster_bwd_abs(int img_h, int img_w, int block_width, int n, 
                                   int recs_packed, void *grad_ws, size_t grad_ws_bytes, const int32_t *tile_order,
                                   const float *colors_pre_clamp, const sgn_raster_opts *opts, sgn_stream_t stream,
                                   sgn_stream_t aux_stream, int first, int last, float *v_xy_abs) {
-    const sgn_raster_opts o = resolve_opts(opts);
     SGN_ARG_CHECK(!window, -13);
     SGN_ARG_CHECK(v_xy_abs != nullptr, -14);
+    // this entry holds the id range to its bounds without a window too (the shared checks: under a window only), at its
+    // place in their order
     SGN_ARG_CHECK(opacity_is_logit >= 0 && opacity_is_logit <= 2, -11);
     SGN_ARG_CHECK(0 <= id_lo && id_lo <= id_hi && id_hi <= n, -9);
-    SGN_ARG_CHECK(img_h > 0 && img_w > 0 && n >= 0, -1);
-    SGN_ARG_CHECK(block_width >= 2 && block_width <= 16, -2);
-    SGN_ARG_CHECK(n_isect >= 0 && n_isect < ((int64_t)1 << 31), -3);
-    if (n == 0) return 0;
-    SGN_ARG_CHECK(v_xy && v_conic && v_colors && v_opacity && grad_ws && opacities && conics, -4);
-    SGN_ARG_CHECK(grad_ws_bytes >= sgn_raster_bwd_workspace_bytes(n), -5);
-    SGN_ARG_CHECK(alpha_clamp_bwd > 0.f && alpha_clamp_bwd < 1.f, -6);
-    SGN_ARG_CHECK(!o.ids_qmask || (block_width == 16 && n < SGN_QMASK_MAX_IDS), -10);
+    const RasterBwdCall c = {img_h, img_w, block_width, n, n_isect, gaussian_ids_sorted, tile_bins, xys, conics, colors,
+                             opacities, opacity_is_logit, id_lo, id_hi, window, background3, final_Ts, final_idx,
+                             v_out_img, v_out_alpha, alpha_clamp_bwd, v_xy, v_conic, v_colors, v_opacity, recs_ws,
+                             recs_ws_bytes, recs_packed, grad_ws, grad_ws_bytes, tile_order, colors_pre_clamp, opts,
+                             stream, aux_stream};
+    const int rc = sgn_raster_bwd_walks(__func__, &absbwd_family, &c, first);
+    if (rc != 0 || n == 0) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (first) SGN_HIP_CHECK(hipMemsetAsync(grad_ws, 0, (size_t)n * SGN_RECORD_FLOATS * sizeof(float), s));
-    if (n_isect > 0) {
-        SGN_ARG_CHECK(gaussian_ids_sorted && tile_bins && xys && conics && colors && opacities && background3 &&
-                          final_Ts && final_idx && v_out_alpha && recs_ws, -7);     // (v_out_img may be NULL: zeros)
-        SGN_ARG_CHECK(recs_ws_bytes >= sgn_raster_workspace_bytes(n, n_isect, &o), -8);
-        if (!recs_packed) {
-            const int rc = sgn_raster_build_rows(n, xys, conics, colors, opacities, opacity_is_logit == 1, id_lo, id_hi,
-                                                 0, recs_ws, recs_ws_bytes, nullptr, stream);
-            if (rc != 0) return rc;
-        }
-        const int tiles_x = (img_w + block_width - 1) / block_width, tiles_y = (img_h + block_width - 1) / block_width;
-        const Rec *rows = (const Rec *)recs_ws;
-        const int n_tiles = tiles_x * tiles_y;
-        // the launch shapes and the fork / join of raster.hip's raster_bwd_impl
-        const bool two_kernel = tile_order != nullptr && block_width == 16;
-        hipStream_t s2 = s;
-        hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-        if (two_kernel && aux_stream != nullptr && (hipStream_t)aux_stream != s && sgn_fork_events(&ev_fork, &ev_join) == 0) {
-            s2 = (hipStream_t)aux_stream;
-            SGN_HIP_CHECK(hipEventRecord(ev_fork, s));
-            SGN_HIP_CHECK(hipStreamWaitEvent(s2, ev_fork, 0));
-        }
-        sgn_timing_begin(SGN_T_RASTER_BWD, s);
-#define SGN_BWD_ARGS                                                                                             \
-    img_w, img_h, block_width, tiles_x, n_tiles, (const int2 *)tile_bins, rows, gaussian_ids_sorted, background3, \
-        final_Ts, final_idx, v_out_img, v_out_alpha, alpha_clamp_bwd, (float *)grad_ws, o.debug_flags, o.adapt_bwd, \
-        o.batch_bwd, tile_order, o.ids_qmask
-#define SGN_LAUNCH_BWD(EX, RM)                                                                                   \
-    do {                                                                                                         \
-        if (!two_kernel)                                                                                         \
-            hipLaunchKernelGGL((raster_absbwd_kernel<EX, RM, 4, true, 0>), dim3(n_tiles * 4), dim3(64), 0, s, SGN_BWD_ARGS); \
-        else {                                                                                                   \
-            hipLaunchKernelGGL((raster_absbwd_kernel<EX, RM, 1, false, 2>), dim3(n_tiles * 4), dim3(64), 0, s2, SGN_BWD_ARGS); \
-            hipLaunchKernelGGL((raster_absbwd_short_kernel<EX, RM>), dim3(n_tiles), dim3(64), 0, s, SGN_BWD_ARGS); \
-        }                                                                                                        \
-    } while (0)
-        if (o.exact_exp) {
-            if (o.reduce_mode) SGN_LAUNCH_BWD(true, 1); else SGN_LAUNCH_BWD(true, 0);
-        } else {
-            if (o.reduce_mode) SGN_LAUNCH_BWD(false, 1); else SGN_LAUNCH_BWD(false, 0);
-        }
-#undef SGN_LAUNCH_BWD
-#undef SGN_BWD_ARGS
-        if (s2 != s) {   // join: the unpack (and everything after) waits for the long-walk kernel
-            SGN_HIP_CHECK(hipEventRecord(ev_join, s2));
-            SGN_HIP_CHECK(hipStreamWaitEvent(s, ev_join, 0));
-        }
-        sgn_timing_end(SGN_T_RASTER_BWD, s);
-    }
     sgn_timing_begin(SGN_T_UNPACK, s);
     if (last)
         hipLaunchKernelGGL(unpack_grads_abs_kernel, dim3(sgn_cdiv(n, 256)), dim3(256), 0, s, n, (const float *)grad_ws,

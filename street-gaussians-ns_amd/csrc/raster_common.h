@@ -4,6 +4,8 @@
 // map of the packed launch, the two ways through a depth list — walk_chase and walk_staged — and the backward body,
 // raster_bwd_tile, which raster.hip instantiates plain and raster_absgrad.hip with the absgrad statistic.  A kernel
 // supplies what it does per entry (and per batch); the traversal, with its prefetch discipline, is written here once.
+// At the end, the host side of the reverse walks: one kernel pointer type, a table of launch shapes per family, and the
+// one launcher and the one check-and-prepare step (both in raster.hip) every backward entry goes through.
 // The arithmetic contract is in raster.hip's header; all units are built with -ffp-contract=off -fno-slp-vectorize, so
 // shared source gives the same bits in each.
 #pragma once
@@ -544,4 +546,67 @@ inline sgn_raster_opts resolve_opts(const sgn_raster_opts *o) {
     return r;
 }
 
+// ---- host side of the reverse walks.  Every backward kernel (raster.hip plain and batched views, raster_absgrad.hip)
+// has this parameter list; only the third and fourth int differ in meaning: (B, tiles_x) for a single view,
+// (tiles_x, tiles_per_view) for batched views.
+using RasterBwdKernel = void (*)(int W, int H, int i2, int i3, int n_tiles, const int2 *bins, const Rec *recs,
+                                 const int32_t *ids, const float *bg, const float *final_T, const int32_t *final_idx,
+                                 const float *v_out, const float *v_out_alpha, float alpha_clamp, float *grad_ws, int dbg,
+                                 int adapt_thresh, int batch_thresh, const int32_t *tile_order, int use_qm);
+// A family's launch shapes (raster.hip "Launch shapes of the backward"), each [exact_exp][reduce_mode]; every unit
+// defines the table of its own kernels.  adaptive == nullptr: the family always runs the two-kernel scheme.
+struct RasterBwdFamily {
+    RasterBwdKernel adaptive[2][2];     // the in-kernel adaptive split: no launch order / tiles other than 16x16
+    RasterBwdKernel long_walk[2][2];    // two-kernel scheme: order[0..n_long), four lean waves per tile
+    RasterBwdKernel short_walk[2][2];   //                    the rest, one wave per tile
+};
+// the kernel arguments; n_tiles is also the launch grid's tile count, o the resolved options
+struct RasterBwdArgs {
+    int W, H, i2, i3, n_tiles;
+    const int2 *bins;
+    const Rec *recs;
+    const int32_t *ids;
+    const float *bg, *final_T;
+    const int32_t *final_idx;
+    const float *v_out, *v_out_alpha;
+    float alpha_clamp;
+    float *grad_ws;
+    const int32_t *tile_order;
+    sgn_raster_opts o;
+};
+// what sgn_raster_bwd, sgn_raster_bwd_part and sgn_raster_bwd_abs are called with (include/sgn_rast.h)
+struct RasterBwdCall {
+    int img_h, img_w, block_width, n;
+    int64_t n_isect;
+    const int32_t *gaussian_ids_sorted, *tile_bins;
+    const float *xys, *conics, *colors, *opacities;
+    int opacity_is_logit, id_lo, id_hi, window;
+    const float *background3, *final_Ts;
+    const int32_t *final_idx;
+    const float *v_out_img, *v_out_alpha;
+    float alpha_clamp_bwd;
+    float *v_xy, *v_conic, *v_colors, *v_opacity;
+    void *recs_ws;
+    size_t recs_ws_bytes;
+    int recs_packed;
+    void *grad_ws;
+    size_t grad_ws_bytes;
+    const int32_t *tile_order;
+    const float *colors_pre_clamp;
+    const sgn_raster_opts *opts;
+    sgn_stream_t stream, aux_stream;
+};
+
 }  // namespace
+
+// Both defined in raster.hip.  C linkage: Rec and the types above live in each unit's unnamed namespace (the kernels'
+// symbols carry it), so a C++ function over them could not be defined in another unit; the layouts are one header's.
+// sgn_raster_bwd_launch: fork to `aux` (two_kernel, aux lent and not `s`, events available), SGN_T_RASTER_BWD, the
+// family's kernels for a.o — adaptive on s (grid 4 * n_tiles), or long_walk on aux (4 * n_tiles) then short_walk on s
+// (n_tiles) — and the join.
+extern "C" int sgn_raster_bwd_launch(const RasterBwdFamily *family, const RasterBwdArgs *a, int two_kernel,
+                                     hipStream_t s, hipStream_t aux);
+// sgn_raster_bwd_walks: the single-view entries up to their unpack — the argument checks (reported under `fn`), the
+// workspace clear (clear_ws), the row build (unless c.recs_packed) and, n_isect > 0, the launch.  n == 0: nothing queued.
+extern "C" int sgn_raster_bwd_walks(const char *fn, const RasterBwdFamily *family, const RasterBwdCall *c,
+                                    int clear_ws);

@@ -14,13 +14,17 @@ void sgn_timing_begin(int slot, void *stream);
 void sgn_timing_end(int slot, void *stream);
 int sgn_fork_events(hipEvent_t *fork, hipEvent_t *join);   // api.cpp: cached per (thread, device)
 
-#define SGN_ARG_CHECK(cond, code)                                              \
+// SGN_ARG_CHECK_FN: the message carries `fn` — checks shared by several entries are handed the public entry's name.
+// (`text` is stringized where the condition is written, before its macros such as HALO expand.)
+#define SGN_ARG_CHECK_TEXT_(fn, cond, text, code)                              \
     do {                                                                       \
         if (!(cond)) {                                                         \
-            sgn_set_error("%s: argument check failed: %s", __func__, #cond);   \
+            sgn_set_error("%s: argument check failed: %s", (fn), text);        \
             return (code);                                                     \
         }                                                                      \
     } while (0)
+#define SGN_ARG_CHECK_FN(fn, cond, code) SGN_ARG_CHECK_TEXT_(fn, cond, #cond, code)
+#define SGN_ARG_CHECK(cond, code) SGN_ARG_CHECK_TEXT_(__func__, cond, #cond, code)
 
 #define SGN_HIP_CHECK(expr)                                                    \
     do {                                                                       \

@@ -7,10 +7,14 @@ import torch
 from sgn_rast import _lib
 
 
-def _call(lib, n=4, window=0, v_xy_abs=1, grad_ws_bytes=4 * 48, block=16, first=1, last=1):
+ENTRY_TAILS = {"sgn_raster_bwd": 0, "sgn_raster_bwd_part": 2, "sgn_raster_bwd_abs": 3}   # of (first, last, v_xy_abs)
+
+
+def _call(lib, n=4, window=0, v_xy_abs=1, grad_ws_bytes=4 * 48, block=16, first=1, last=1, entry="sgn_raster_bwd_abs"):
     p = 1                                          # a non-NULL address nothing reads: every case fails its check first
-    return lib.sgn_raster_bwd_abs(8, 8, block, n, 3, p, p, p, p, p, p, 0, 0, n, window, p, p, p, p, p, 0.99, p, p, p, p,
-                                  p, n * 48, 1, p, grad_ws_bytes, None, None, None, None, None, first, last, v_xy_abs)
+    tail = (first, last, v_xy_abs)[:ENTRY_TAILS[entry]]
+    return getattr(lib, entry)(8, 8, block, n, 3, p, p, p, p, p, p, 0, 0, n, window, p, p, p, p, p, 0.99, p, p, p, p,
+                               p, n * 48, 1, p, grad_ws_bytes, None, None, None, None, None, *tail)
 
 
 def test_argument_errors_are_reported_without_a_gpu():
@@ -25,6 +29,19 @@ def test_argument_errors_are_reported_without_a_gpu():
     assert _call(lib, block=32) == -2 and b"block_width" in lib.sgn_last_error()
     assert _call(lib, n=0, grad_ws_bytes=0) == 0                   # nothing to do is not an error
     assert lib.sgn_raster_bwd_workspace_bytes(4) == 4 * 48         # slots 9, 10 live in the row the plain walks use
+
+
+@pytest.mark.parametrize("entry", sorted(ENTRY_TAILS))
+def test_shared_checks_report_the_entry_that_was_called(entry):
+    """The three single-view backward entries share their checks; a failure carries the name of the entry the caller
+    used, and the condition's text its argument names."""
+    lib = _lib.load()
+    assert _call(lib, block=32, entry=entry) == -2
+    err = lib.sgn_last_error()
+    assert err.startswith(entry.encode() + b":") and b"block_width" in err, err
+    assert _call(lib, grad_ws_bytes=4 * 48 - 1, entry=entry) == -5
+    err = lib.sgn_last_error()
+    assert err.startswith(entry.encode() + b":") and b"grad_ws_bytes" in err, err
 
 
 def test_unsupported_call_shapes_raise_before_any_launch():
