@@ -1160,6 +1160,32 @@ int sgn_aa_opacity_fwd(int n, const float *opacity_logits, const float *compensa
 int sgn_aa_opacity_bwd(int n, const float *opacity_logits, const float *compensation, const float *v_opacities,
                        float *v_opacity_logits, float *v_compensation, sgn_stream_t stream);
 
+/* BILATERAL GRID (per-image colour correction: cameras of a street rig meter on their own; gsplat's trainer answers
+ * with a bilateral grid per image, the original Street Gaussians code with a 3x4 affine per image / sensor, which is the
+ * 1 x 1 x 1 grid).  grid: g[L, Hg, Wg, 12] float32, cell-major, coefficient 4 r + c = row r, column c of a 3x4 affine
+ * (c = 3: the bias), 16-byte aligned.  rgb / out / v_out / v_rgb: the first n_pix pixels, row-major, of an H x W image,
+ * 3 floats each (0 <= n_pix <= H * W; the whole image is n_pix = H * W).  For pixel (i, j) with colour p = (R, G, B):
+ *     gx = (j + 0.5) / W * (Wg - 1)          gy = (i + 0.5) / H * (Hg - 1)          (IEEE division)
+ *     luma = 0.299 R + 0.587 G + 0.114 B     gz = clamp(luma, 0, 1) * (L - 1)
+ *     x0 = floor(gx), x1 = min(x0 + 1, Wg - 1), fx = gx - x0                        and the same for y and z
+ *     A = the trilinear mix of the eight cells as NESTED LERPS a + f * (b - a): z innermost, then x, then y
+ *     out_r = A[r,0] R + A[r,1] G + A[r,2] B + A[r,3]                               (left to right)
+ * i.e. grid_sample(align_corners=True, padding_mode="border") on (x, y, luma) in [0,1]^3 and the affine.  The lerp form
+ * is part of the contract: a grid whose cells are all the identity affine returns rgb bit for bit.  fp32, no contraction.
+ * sgn_bilagrid_slice_bwd, with w_cell the product of a cell's three lerp weights, dA = A|z1 - A|z0 (the innermost lerps'
+ * differences mixed over x and y as A is; zero when z0 == z1) and lw the three luma weights:
+ *     v_grid[cell][4 r + c] += w_cell * v_out_r * (R, G, B, 1)[c]
+ *     v_rgb_k = sum_r v_out_r A[r,k] + lw_k * (L - 1) * [0 < luma < 1] * sum_r v_out_r * (dA[r,:] . (R, G, B, 1))
+ * v_grid [L, Hg, Wg, 12] is ADDED INTO (the caller clears it) with float atomics after an on-chip sum: its last bits
+ * depend on arrival order; out and v_rgb are plain stores, bit-identical from run to run.  v_rgb / v_grid: either may be
+ * NULL (not wanted); both NULL returns 0 without a launch, as n_pix == 0 does.  No workspace.
+ * Return codes: -1 L, Hg, Wg, H or W < 1, H or W > 16384, more than 2^27 cells, n_pix outside [0, H * W]; -2 a required
+ * pointer is NULL; -3 grid is not 16-byte aligned.  csrc/bilagrid.hip. */
+int sgn_bilagrid_slice_fwd(int L, int Hg, int Wg, const float *grid, int H, int W, int n_pix, const float *rgb,
+                           float *out, sgn_stream_t stream);
+int sgn_bilagrid_slice_bwd(int L, int Hg, int Wg, const float *grid, int H, int W, int n_pix, const float *rgb,
+                           const float *v_out, float *v_rgb, float *v_grid, sgn_stream_t stream);
+
 /* BATCHED VIEWS (no upstream counterpart; gsplat 1.x takes [C] cameras per call).  B = n_views cameras share one image
  * size (img_h, img_w), 16x16 tiles and one set of N Gaussians in the fused front end's raw form (means, log-scales, raw
  * quaternions, opacity logits, features_dc [N,1,3], features_rest [N,k-1,3]; no scene graph).  Row b*N + i of every

@@ -726,6 +726,39 @@ int sgn_frames_pack(int h, int w, int n_panels, const sgn_panel *panels, uint8_t
     return sgn_frames_pack_launch(h, w, n_panels, panels, canvas, canvas_w, stream);
 }
 
+// ---------------------------------------------------------------- bilateral-grid colour correction (bilagrid.hip)
+namespace {
+// the checks the two entries share; 1: nothing to do
+int bilagrid_check(const char *fn, int L, int Hg, int Wg, const float *grid, int H, int W, int n_pix, const float *rgb) {
+    constexpr int MAX_DIM = 16384;                     // 32-bit element indices: 16384 * 16384 * 3 < 2^31
+    SGN_ARG_CHECK_FN(fn, L >= 1 && Hg >= 1 && Wg >= 1 && H >= 1 && W >= 1, -1);
+    SGN_ARG_CHECK_FN(fn, H <= MAX_DIM && W <= MAX_DIM, -1);
+    SGN_ARG_CHECK_FN(fn, (int64_t)L * Hg * Wg <= ((int64_t)1 << 27), -1);          // 12 floats per cell, 32-bit offsets
+    SGN_ARG_CHECK_FN(fn, n_pix >= 0 && (int64_t)n_pix <= (int64_t)H * W, -1);
+    if (n_pix == 0) return 1;
+    SGN_ARG_CHECK_FN(fn, grid && rgb, -2);
+    SGN_ARG_CHECK_FN(fn, ((uintptr_t)grid & 15) == 0, -3);                         // cells are read 16 bytes at a time
+    return 0;
+}
+}  // namespace
+
+SGN_EXPORT
+int sgn_bilagrid_slice_fwd(int L, int Hg, int Wg, const float *grid, int H, int W, int n_pix, const float *rgb,
+                           float *out, sgn_stream_t stream) {
+    if (int rc = bilagrid_check(__func__, L, Hg, Wg, grid, H, W, n_pix, rgb)) return rc < 0 ? rc : 0;
+    SGN_ARG_CHECK(out, -2);
+    return sgn_bilagrid_slice_fwd_launch(L, Hg, Wg, grid, H, W, n_pix, rgb, out, stream);
+}
+
+SGN_EXPORT
+int sgn_bilagrid_slice_bwd(int L, int Hg, int Wg, const float *grid, int H, int W, int n_pix, const float *rgb,
+                           const float *v_out, float *v_rgb, float *v_grid, sgn_stream_t stream) {
+    if (int rc = bilagrid_check(__func__, L, Hg, Wg, grid, H, W, n_pix, rgb)) return rc < 0 ? rc : 0;
+    SGN_ARG_CHECK(v_out, -2);
+    if (v_rgb == nullptr && v_grid == nullptr) return 0;                           // neither gradient is wanted
+    return sgn_bilagrid_slice_bwd_launch(L, Hg, Wg, grid, H, W, n_pix, rgb, v_out, v_rgb, v_grid, stream);
+}
+
 // ---------------------------------------------------------------- kernel timing (bench/profiles)
 // Opt-in: when enabled every timed launch is bracketed by hipEventRecord on the SAME stream the
 // kernel is launched on; sgn_timing_get() synchronises the recorded events and sums them.

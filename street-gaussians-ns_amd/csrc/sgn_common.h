@@ -108,6 +108,12 @@ int sgn_gt_downscale_launch(int h, int w, int oh, int ow, const unsigned char *i
 int sgn_frames_pack_launch(int h, int w, int n_panels, const sgn_panel *panels, unsigned char *canvas, int canvas_w,
                            sgn_stream_t stream);
 
+// bilagrid.hip: the launches behind sgn_bilagrid_slice_fwd / _bwd (api.cpp checks the arguments)
+int sgn_bilagrid_slice_fwd_launch(int L, int Hg, int Wg, const float *grid, int H, int W, int n_pix, const float *rgb,
+                                  float *out, sgn_stream_t stream);
+int sgn_bilagrid_slice_bwd_launch(int L, int Hg, int Wg, const float *grid, int H, int W, int n_pix, const float *rgb,
+                                  const float *v_out, float *v_rgb, float *v_grid, sgn_stream_t stream);
+
 // Batched views (include/sgn_rast.h "Batched views"): the camera table travels BY VALUE as a kernel argument (SGPRs /
 // the kernarg segment, no device buffer, no copy), one entry per view; the host fills it from sgn_view_cam rows.
 struct SgnViews {

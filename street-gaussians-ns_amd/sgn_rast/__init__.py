@@ -12,9 +12,11 @@ the outbound mirror of the feed (``frames``: a frame's eval outputs packed into 
 pinned memory behind the next render), the feature channels composited over the RGB pass's depth list (``features``:
 K per-Gaussian values in one walk per 16 channels with gradients, the differentiable expected depth, the semantic
 cross-entropy), LiDAR depth supervision (``lidar``: sweeps splatted to a per-pixel target, the fused depth loss on the
-expected depth, the evaluation depth metrics), the call-site replay used by bench/smoke/tests (``step``) and the deterministic synthetic scenes
+expected depth, the evaluation depth metrics), per-image colour correction (``appearance``: bilateral grids of 3x4 affines
+sliced by one fused kernel pair, the per-image affine as the 1 x 1 x 1 grid, the total-variation prior), the call-site replay used by bench/smoke/tests (``step``) and the deterministic synthetic scenes
 (``scenes``).  Sub-modules are imported on demand; none of them has a CPU fallback.
 """
+from .appearance import BilateralGrids, slice_image, total_variation  # noqa: F401
 from .features import (  # noqa: F401
     expected_depth,
     rasterize_features,

@@ -166,6 +166,8 @@ SIGNATURES = {
     "sgn_depth_metrics": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sgn_aa_opacity_fwd": (_i, [_i, _vp, _vp, _vp, _vp]),
     "sgn_aa_opacity_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sgn_bilagrid_slice_fwd": (_i, [_i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "sgn_bilagrid_slice_bwd": (_i, [_i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

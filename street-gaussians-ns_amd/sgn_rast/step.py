@@ -568,7 +568,7 @@ def train_step(P: Dict[str, torch.Tensor], cam: Camera, w_img: torch.Tensor, w_a
                ssim_lambda: float = 0.2, loss_fn=None, caller_syncs: bool = False, zero_grad: bool = True,
                mask: Optional[torch.Tensor] = None, lidar_depth: Optional[torch.Tensor] = None,
                depth_loss_mult: float = 0.1, depth_loss_kind: str = "l1", rasterize_mode: str = "classic",
-               absgrad: bool = False, densifier=None, step: int = 0, **fused_kw) -> SimpleNamespace:
+               absgrad: bool = False, densifier=None, step: int = 0, appearance=None, **fused_kw) -> SimpleNamespace:
     """One "train-step image": project fwd -> SH fwd -> rasterize(return_alpha) fwd -> scalar loss ->
     full backward to means / log-scales / raw quats / opacity logits / SH coefficients (the metric's definition,
     SURVEY.md §8d: the operator sequence; ``caller_syncs=True`` adds the two host syncs of the reference's own model
@@ -586,8 +586,25 @@ def train_step(P: Dict[str, torch.Tensor], cam: Camera, w_img: torch.Tensor, w_a
     ``absgrad=True`` (``fused=True`` only; ``ValueError`` otherwise): the colour pass sums the absolute screen-space
     gradients, ``out.xys.absgrad`` [N,2] after the backward.  ``densifier`` (a :class:`sgn_rast.densify.Densifier`):
     its ``after_train(step, ...)`` runs behind the backward with this render's ``xys.grad`` — or, under
-    ``DensifyConfig(absgrad=True)``, its ``xys.absgrad`` — radii and image size."""
+    ``DensifyConfig(absgrad=True)``, its ``xys.absgrad`` — radii and image size.
+    ``appearance=(grids, index)`` — a :class:`sgn_rast.appearance.BilateralGrids` module or its ``[num, L, Hg, Wg, 12]``
+    tensor, and the image's (or sensor's) number — corrects ``out.rgb`` with ``appearance.slice_image`` after the sky
+    composite and before the photometric loss, whose own clamp and mask then act on the corrected colour; the
+    uncorrected image is kept as ``out.rgb_raw``, the grids' gradient lands in ``grids.grad`` (this step does not reset
+    it).  It needs ``gt`` (``ValueError`` before the render otherwise).  Out of scope: ``train_step_views``, the
+    scene-graph step and the data-parallel exchange of the grids' gradients do not take it."""
     antialiased = antialiased_mode(rasterize_mode)
+    if appearance is not None:
+        from . import appearance as _appearance
+        if gt is None:
+            raise ValueError("appearance corrects the image the photometric loss compares: pass gt as well")
+        app_grids, app_index = appearance
+        if isinstance(app_grids, _appearance.BilateralGrids):
+            app_grids = app_grids.grids
+        if not isinstance(app_grids, torch.Tensor) or app_grids.dim() != 5 or app_grids.shape[-1] != 12 \
+                or app_grids.dtype != torch.float32 or isinstance(app_index, bool) or not isinstance(app_index, int) \
+                or not 0 <= app_index < app_grids.shape[0]:
+            raise ValueError("appearance must be (grids [num, L, Hg, Wg, 12] float32 or BilateralGrids, index in range)")
     if absgrad and not fused:
         raise ValueError("absgrad is not supported on the drop-in operators (gsplat 0.1.x surface): use fused=True")
     if densifier is not None and densifier.cfg.absgrad and not absgrad:
@@ -621,6 +638,9 @@ def train_step(P: Dict[str, torch.Tensor], cam: Camera, w_img: torch.Tensor, w_a
     if sky is not None:
         composite_sky(out, cam, sky["base"], sky["c2w"], train=sky.get("train", True), fused=fused,
                       sky_fn=sky.get("fn"))
+    if appearance is not None:
+        out.rgb_raw = out.rgb
+        out.rgb = _appearance.slice_image(app_grids, app_index, out.rgb)
     n_pix = cam.height * cam.width
     if gt is not None:
         if loss_fn is not None:                                                        # tests: the oracle's loss
