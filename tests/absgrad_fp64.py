@@ -90,90 +90,135 @@ def make_scene(seed, n_small=230, n_large=10, n_cluster=60, block=16, single=Fal
                            w_alpha=rng.uniform(-1, 1, (H, W)).astype(np.float32))
 
 
-def reverse_walk(sc, v_img, v_alpha_img, alpha_clamp_bwd=0.99, clamp_zeroes_grad=False):
-    """-> SimpleNamespace(signed [N,2], absolute [N,2], adjacent [N] bool, visible [N] bool, img [H,W,3],
-    alpha [H,W], n_stopped) in float64; `v_img` [H,W,3] / `v_alpha_img` [H,W]: the loss's gradients w.r.t. the two
-    images."""
-    f8 = np.float64
+def walk(sc, v_img, v_alpha_img, alpha_clamp_bwd=0.99, clamp_zeroes_grad=False, *, on_pair, on_tile=None, id_range=None,
+         dtype=np.float64, exp=np.exp, opacities=None, sigma_adjacent=False):
+    """The contract above, tile by tile: the forward compositing, then the reverse walk.  What is summed from it is the
+    caller's business — `reverse_walk` below sums the screen-space gradient, `tests/raster_fp64.py` every output:
+        on_tile(t)  once per tile after its forward: t.y0, t.y1, t.x0, t.x1, t.lst (the depth list), t.C [P,3], t.T [P]
+                    (T_final), t.weights (per entry alpha T where it was composited, else 0), t.last [P]
+        on_pair(p)  once per entry of the reverse walk some pixel evaluates, back to front: p.tile (the on_tile record),
+                    p.g, p.k, p.valid [P], p.dx, p.dy, p.e (= exp(-sigma)), p.av, p.alpha_b, p.T_before, p.v_alpha,
+                    p.v_sigma (the last two are 0 on pixels that are not valid WHERE av is finite), p.vo [P,3]
+    `dtype`: every array and constant, hence every operation, in that type (float32: an emulation of a float32
+    implementation).  `exp`: the exponential (called on -sigma).  `id_range=(lo, hi)`: the sub-list of those ids, same
+    relative order.  `opacities`: instead of the scene's.  `sigma_adjacent`: a pair with |sigma| <= 1e-5 (the sigma < 0
+    test) is threshold-adjacent too.
+    -> SimpleNamespace(adjacent [N], visible [N], adjacent_px [H,W], n_stopped, list_len [tiles], walk_len [tiles])."""
+    dt = np.dtype(dtype).type
     n, B = sc.n, sc.block
-    xys, conics, colors, opac, bg = (np.asarray(a, f8) for a in (sc.xys, sc.conics, sc.colors, sc.opacities,
-                                                                 sc.background))
-    v_img, v_alpha_img = np.asarray(v_img, f8), np.asarray(v_alpha_img, f8)
+    xys, conics, colors, bg = (np.asarray(a, dt) for a in (sc.xys, sc.conics, sc.colors, sc.background))
+    opac = np.asarray(sc.opacities if opacities is None else opacities, dt)
+    v_img, v_alpha_img = np.asarray(v_img, dt), np.asarray(v_alpha_img, dt)
     tiles_x, tiles_y = (sc.W + B - 1) // B, (sc.H + B - 1) // B
     mnx, mny, mxx, mxy = tile_bbox(sc.xys, sc.radii, tiles_x, tiles_y, B)
     by_depth = np.lexsort((np.arange(n), sc.depths))         # float32 depth, ties by id
-    signed, absolute = np.zeros((n, 2)), np.zeros((n, 2))
+    lo, hi = (0, n) if id_range is None else id_range
     adjacent, visible = np.zeros(n, bool), np.zeros(n, bool)
+    adjacent_px = np.zeros((sc.H, sc.W), bool)
     n_stopped = 0                                            # pixels whose walk ended at the 1e-4 test
-    img, alpha_img = np.empty((sc.H, sc.W, 3)), np.empty((sc.H, sc.W))
-    third = 1.0 / 255.0
+    list_len, walk_len = [], []
+    half, one, zero, a_max, a_bwd, t_min = dt(0.5), dt(1.0), dt(0.0), dt(0.999), dt(alpha_clamp_bwd), dt(1e-4)
+    third = one / dt(255.0)
     for ty in range(tiles_y):
         for tx in range(tiles_x):
             y0, y1, x0, x1 = ty * B, min((ty + 1) * B, sc.H), tx * B, min((tx + 1) * B, sc.W)
-            py, px = (a.reshape(-1) for a in np.meshgrid(np.arange(y0, y1) + 0.5, np.arange(x0, x1) + 0.5,
-                                                         indexing="ij"))
-            lst = [g for g in by_depth if sc.radii[g] > 0 and mnx[g] <= tx < mxx[g] and mny[g] <= ty < mxy[g]]
+            py, px = (a.reshape(-1).astype(dt) for a in np.meshgrid(np.arange(y0, y1) + 0.5, np.arange(x0, x1) + 0.5,
+                                                                    indexing="ij"))
+            lst = [g for g in by_depth if lo <= g < hi and sc.radii[g] > 0 and mnx[g] <= tx < mxx[g]
+                   and mny[g] <= ty < mxy[g]]
             P = px.size
-            T, C, last = np.ones(P), np.zeros((P, 3)), np.full(P, -1)
-            live, near_stop = np.ones(P, bool), np.zeros(P, bool)
-            pairs = []                                                      # per entry: dx, dy, sigma, av
+            T, C, last = np.ones(P, dt), np.zeros((P, 3), dt), np.full(P, -1)
+            live, near_stop, near_px = np.ones(P, bool), np.zeros(P, bool), np.zeros(P, bool)
+            pairs, weights = [], []                                         # per entry: dx, dy, sigma, e, av
             for k, g in enumerate(lst):
                 dx, dy = xys[g, 0] - px, xys[g, 1] - py
                 A, Bc, Cc = conics[g]
-                sigma = 0.5 * (A * dx * dx + Cc * dy * dy) + Bc * dx * dy
-                av = opac[g] * np.exp(-sigma)
-                alpha = np.minimum(0.999, av)
-                pairs.append((dx, dy, sigma, av))
+                sigma = half * (A * dx * dx + Cc * dy * dy) + Bc * dx * dy
+                e = exp(-sigma)
+                av = opac[g] * e
+                alpha = np.minimum(a_max, av)
+                pairs.append((dx, dy, sigma, e, av))
                 # a pair float32 may put on the other side of the 1/255 test or of a clamp (pixels still compositing)
-                if (live & (sigma >= 0) & ((np.abs(alpha - third) <= ADJ) | (np.abs(av - 0.999) <= ADJ) |
-                                           (np.abs(av - alpha_clamp_bwd) <= ADJ))).any():
+                near = live & (sigma >= 0) & ((np.abs(alpha - third) <= ADJ) | (np.abs(av - a_max) <= ADJ) |
+                                              (np.abs(av - a_bwd) <= ADJ))
+                if sigma_adjacent:
+                    near |= live & (np.abs(sigma) <= ADJ)
+                if near.any():
                     adjacent[g] = True
+                    near_px |= near
                 valid = live & (sigma >= 0) & (alpha >= third)
-                nT = T * (1.0 - alpha)
-                near_stop |= valid & (np.abs(nT - 1e-4) <= ADJ * 1e-4)
-                stop = valid & (nT <= 1e-4)
+                nT = T * (one - alpha)
+                near_stop |= valid & (np.abs(nT - t_min) <= ADJ * 1e-4)
+                stop = valid & (nT <= t_min)
                 acc = valid & ~stop
-                C += np.where(acc, alpha * T, 0.0)[:, None] * colors[g][None, :]
+                w = np.where(acc, alpha * T, zero)
+                weights.append(w)
+                C += w[:, None] * colors[g][None, :]
                 T = np.where(acc, nT, T)
                 last = np.where(acc, k, last)
                 live &= ~stop
             n_stopped += int((~live).sum())
-            img[y0:y1, x0:x1] = (C + T[:, None] * bg[None, :]).reshape(y1 - y0, x1 - x0, 3)
-            alpha_img[y0:y1, x0:x1] = (1.0 - T).reshape(y1 - y0, x1 - x0)
+            list_len.append(len(lst))
+            walk_len.append(int(last.max()) + 1)
+            adjacent_px[y0:y1, x0:x1] = (near_px | near_stop).reshape(y1 - y0, x1 - x0)
+            tile = SimpleNamespace(y0=y0, y1=y1, x0=x0, x1=x1, lst=lst, C=C, T=T, weights=weights, last=last)
+            if on_tile is not None:
+                on_tile(tile)
             # ---- the reverse walk
             vo = v_img[y0:y1, x0:x1].reshape(P, 3)
             voa = v_alpha_img[y0:y1, x0:x1].reshape(P)
             part = last >= 0                                   # pixels something was composited onto
             Tf = T.copy()
             c0 = Tf * (voa - vo @ bg)
-            bv = np.zeros(P)
+            bv = np.zeros(P, dt)
             for k in range(len(lst) - 1, -1, -1):
                 g = lst[k]
-                dx, dy, sigma, av = pairs[k]
-                alpha_b = np.minimum(alpha_clamp_bwd, av)
+                dx, dy, sigma, e, av = pairs[k]
+                alpha_b = np.minimum(a_bwd, av)
                 valid = part & (k <= last) & (sigma >= 0) & (alpha_b >= third)
                 if not valid.any():
                     continue
                 visible[g] = True
                 if (valid & near_stop).any():
                     adjacent[g] = True
-                ra = 1.0 / (1.0 - alpha_b)
+                ra = one / (one - alpha_b)
                 Tb = T * ra
                 dotc = vo @ colors[g]
                 v_a = ra * (T * dotc + c0 - bv)
-                v_a = np.where(valid, v_a, 0.0)
-                bv = bv + np.where(valid, alpha_b * Tb * dotc, 0.0)
+                v_a = np.where(valid, v_a, zero)
+                bv = bv + np.where(valid, alpha_b * Tb * dotc, zero)
                 T = np.where(valid, Tb, T)
                 if clamp_zeroes_grad:
-                    v_sigma = np.where(av < alpha_clamp_bwd, -alpha_b * v_a, 0.0)
+                    v_sigma = np.where(av < a_bwd, -alpha_b * v_a, zero)
                 else:
                     v_sigma = -av * v_a
-                A, Bc, Cc = conics[g]
-                gx, gy = v_sigma * (A * dx + Bc * dy), v_sigma * (Bc * dx + Cc * dy)
-                signed[g] += (gx.sum(), gy.sum())
-                absolute[g] += (np.abs(gx).sum(), np.abs(gy).sum())
-    return SimpleNamespace(signed=signed, absolute=absolute, adjacent=adjacent, visible=visible, img=img,
-                           alpha=alpha_img, n_stopped=n_stopped)
+                on_pair(SimpleNamespace(tile=tile, g=g, k=k, valid=valid, dx=dx, dy=dy, e=e, av=av, alpha_b=alpha_b,
+                                        T_before=Tb, v_alpha=v_a, v_sigma=v_sigma, vo=vo))
+    return SimpleNamespace(adjacent=adjacent, visible=visible, adjacent_px=adjacent_px, n_stopped=n_stopped,
+                           list_len=np.array(list_len), walk_len=np.array(walk_len))
+
+
+def reverse_walk(sc, v_img, v_alpha_img, alpha_clamp_bwd=0.99, clamp_zeroes_grad=False):
+    """-> SimpleNamespace(signed [N,2], absolute [N,2], adjacent [N] bool, visible [N] bool, img [H,W,3],
+    alpha [H,W], n_stopped) in float64; `v_img` [H,W,3] / `v_alpha_img` [H,W]: the loss's gradients w.r.t. the two
+    images."""
+    conics, bg = np.asarray(sc.conics, np.float64), np.asarray(sc.background, np.float64)
+    signed, absolute = np.zeros((sc.n, 2)), np.zeros((sc.n, 2))
+    img, alpha_img = np.empty((sc.H, sc.W, 3)), np.empty((sc.H, sc.W))
+
+    def on_tile(t):
+        img[t.y0:t.y1, t.x0:t.x1] = (t.C + t.T[:, None] * bg[None, :]).reshape(t.y1 - t.y0, t.x1 - t.x0, 3)
+        alpha_img[t.y0:t.y1, t.x0:t.x1] = (1.0 - t.T).reshape(t.y1 - t.y0, t.x1 - t.x0)
+
+    def on_pair(p):
+        A, Bc, Cc = conics[p.g]
+        gx, gy = p.v_sigma * (A * p.dx + Bc * p.dy), p.v_sigma * (Bc * p.dx + Cc * p.dy)
+        signed[p.g] += (gx.sum(), gy.sum())
+        absolute[p.g] += (np.abs(gx).sum(), np.abs(gy).sum())
+
+    w = walk(sc, v_img, v_alpha_img, alpha_clamp_bwd, clamp_zeroes_grad, on_pair=on_pair, on_tile=on_tile)
+    return SimpleNamespace(signed=signed, absolute=absolute, adjacent=w.adjacent, visible=w.visible, img=img,
+                           alpha=alpha_img, n_stopped=w.n_stopped)
 
 
 @lru_cache(maxsize=None)
