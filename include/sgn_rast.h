@@ -1005,6 +1005,53 @@ int sgn_densify_apply(int n, int n_out, int n_split_samples, int64_t noise_rows,
                       const int32_t *roles, int32_t *src /*[n_out]*/, int32_t *kind /*[n_out]*/, const void *ws,
                       size_t ws_bytes, sgn_stream_t stream);
 
+/* FIXED-BUDGET MCMC REFINEMENT ("3D Gaussian Splatting as Markov Chain Monte Carlo"; gsplat's MCMCStrategy; no
+ * counterpart in the reference; decided here from the published algorithm, unpinned): dead Gaussians teleported onto
+ * live ones sampled by opacity, growth up to a cap, opacity-gated noise on the means.  The arithmetic contract is the
+ * header comment of csrc/mcmc.hip; sgn_rast.mcmc.MCMCDensifier's torch engine restates it and takes the same integer
+ * decisions bit for bit.  One phase (relocate, or grow) is weights -> scan -> [host reads totals2] -> draw ->
+ * relocation -> apply over one caller-allocated workspace, ws >= sgn_mcmc_workspace_bytes(n) (0 for n <= 0), which
+ * carries the block sums, the totals, the per-row draw counts and the per-row owning draw between the steps.  All
+ * asynchronous on `stream`; n == 0 (and k == 0 where there is a k) returns 0 without a launch.  Return codes: -1 n / k
+ * out of range (n + k must fit an int32; relocate: k <= n), -2 n_max outside [1, 51], -3 a required pointer is NULL (or
+ * relocate's outputs[i] != inputs[i], grow's outputs[i] == inputs[i]), -4 mode not 0 / 1, -5 workspace too small,
+ * -6 bad tensor table, -7 quats not 16-byte aligned.
+ *
+ * sgn_mcmc_weights: one lane per row.  o = 1 / (1 + exp(-(double)logit)); dead[i] = o <= (double)min_opacity;
+ *     w[i] = floor(o * 2^24 + 0.5), and 0 for a dead row when relocate != 0.
+ * sgn_mcmc_scan: prefix[i] = the exclusive int64 sum of w (a block scan, then a scan of the block sums);
+ *     dead_rows[j] = the j-th dead row in row order; totals2 (DEVICE int64[2], read back once per phase) = [n_dead, total].
+ * sgn_mcmc_draw: one lane per draw j < k: h = mix64(mix64(j + 1) ^ key), t = (h >>> 1) mod total, src[j] = the row with
+ *     prefix[s] <= t < prefix[s] + w[s] (binary search); then ratio[j] = min(n_max, 1 + number of draws that chose
+ *     src[j]).  total == 0 is the caller's case to skip.
+ * sgn_mcmc_relocation: staging[j] = {logit', log_scales'[3]} of draw j, in fp64 from row src[j]'s CURRENT logit and
+ *     log-scales (nothing has been written yet), rounded to fp32 once.
+ * sgn_mcmc_apply: `count` (<= 24) tensors by HOST arrays of DEVICE pointers inputs[i] / outputs[i] (contiguous fp32),
+ *     row_floats[i] and roles[i]: 0 a parameter whose target rows copy their source row, 1 the opacity logits
+ *     (row_floats 1), 2 the log-scales (row_floats 3), 3 an Adam moment.  mode 0, relocate, IN PLACE (outputs[i] ==
+ *     inputs[i], n rows): row targets[j] becomes row src[j] with the staged values, row src[j] gets the staged values
+ *     and zeroed moments; targets' moments and every other row keep their bits.  mode 1, grow (outputs of n + k rows,
+ *     never aliased; targets ignored): rows < n copy, sources with the staged values and their moments unchanged; row
+ *     n + j copies src[j] with the staged values and zero moments.
+ * sgn_mcmc_noise: the per-step pass, one lane per row: three hashed normal deviates (fp64 Box-Muller on the row's own
+ *     counter hash, rounded to fp32; z_out [n,3] nullable receives them), then in fp32
+ *     means += R diag(exp(log_scales))^2 R^T ((z * g) * scaler), g = 1 / (1 + exp(-100 ((1 - sigmoid(logit)) - 0.995))). */
+size_t sgn_mcmc_workspace_bytes(int n);
+int sgn_mcmc_weights(int n, const float *opacity_logits /*[n]*/, float min_opacity, int relocate, int32_t *w /*[n]*/,
+                     uint8_t *dead /*[n]*/, void *ws, size_t ws_bytes, sgn_stream_t stream);
+int sgn_mcmc_scan(int n, const int32_t *w, const uint8_t *dead, int64_t *prefix /*[n]*/, int32_t *dead_rows /*[n]*/,
+                  void *ws, size_t ws_bytes, int64_t *totals2 /*device int64[2]*/, sgn_stream_t stream);
+int sgn_mcmc_draw(int n, int k, int64_t key, int n_max, const int64_t *prefix, int32_t *src /*[k]*/,
+                  int32_t *ratio /*[k]*/, void *ws, size_t ws_bytes, sgn_stream_t stream);
+int sgn_mcmc_relocation(int n, int k, const float *opacity_logits, const float *log_scales /*[n,3]*/, float min_opacity,
+                        const int32_t *src, const int32_t *ratio, float *staging /*[k,4]*/, sgn_stream_t stream);
+int sgn_mcmc_apply(int mode, int n, int k, const int32_t *src, const int32_t *targets, const float *staging, int count,
+                   const float *const *inputs, float *const *outputs, const int32_t *row_floats, const int32_t *roles,
+                   const void *ws, size_t ws_bytes, sgn_stream_t stream);
+int sgn_mcmc_noise(int n, int64_t key, float scaler, float *means /*[n,3]*/, const float *log_scales /*[n,3]*/,
+                   const float *quats /*[n,4]*/, const float *opacity_logits /*[n]*/, float *z_out /*[n,3] or NULL*/,
+                   sgn_stream_t stream);
+
 /* Exact k-nearest neighbours of 3-D points (SplatfactoModel.populate_modules, sgn_splatfacto.py:260-264: the reference's
  * k_nearest_sklearn, :439-457, sklearn NearestNeighbors(k + 1) with the first column dropped).  For every row i of
  * points [n,3] (finite fp32; non-finite input gives unspecified rows, never an out-of-bounds access): dist[i, :] = the k

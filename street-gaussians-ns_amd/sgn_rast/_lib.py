@@ -70,7 +70,14 @@ SIGNATURES = {
     "sgn_densify_decide": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _vp, _sz, _vp]),
     "sgn_densify_scan": (_i, [_i, _vp, _sz, _vp, _vp]),
     "sgn_densify_apply": (_i, [_i, _i, _i, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "sgn_check_unit_quats": (_i, [_i, _vp, _f, _vp, _vp]),
+    "sgn_mcmc_workspace_bytes": (_sz, [_i]),
+    "sgn_mcmc_weights": (_i, [_i, _vp, _f, _i, _vp, _vp, _vp, _sz, _vp]),
+    "sgn_mcmc_scan": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "sgn_mcmc_draw": (_i, [_i, _i, _i64, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sgn_mcmc_relocation": (_i, [_i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
+    "sgn_mcmc_apply": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sgn_mcmc_noise": (_i, [_i, _i64, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sgn_check_unit_quats":(_i, [_i, _vp, _f, _vp, _vp]),
     "sgn_quat_mul_fwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
     "sgn_quat_mul_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sgn_sh_bwd_multi": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),

@@ -180,6 +180,27 @@ def _hash_normal(base: torch.Tensor, component: int) -> torch.Tensor:
     return (torch.sqrt(-2.0 * torch.log(u1 + 2.0 ** -54)) * torch.cos(2.0 * math.pi * u2)).to(torch.float32)
 
 
+def leaf_like(old: torch.Tensor, data: torch.Tensor) -> torch.Tensor:
+    """A new autograd leaf of the kind ``old`` was (nn.Parameter, as the reference re-creates them, or plain)."""
+    return torch.nn.Parameter(data) if isinstance(old, torch.nn.Parameter) else data.requires_grad_(True)
+
+
+def rebind(params: Dict[str, torch.Tensor], optimizers: Dict[str, torch.optim.Optimizer], name: str,
+           new_param: torch.Tensor, state_fn) -> None:
+    """Swap parameter ``name`` for ``new_param`` in its optimiser, transforming exp_avg / exp_avg_sq with
+    ``state_fn`` (:459-475, :483-504).  The optimiser surgery of every refinement strategy
+    (:class:`Densifier`, :class:`sgn_rast.mcmc.MCMCDensifier`)."""
+    opt, old = optimizers[name], params[name]
+    group = opt.param_groups[0]
+    idx = next(i for i, p in enumerate(group["params"]) if p is old)
+    st = opt.state.pop(old, {})
+    if "exp_avg" in st:
+        st["exp_avg"], st["exp_avg_sq"] = state_fn(st["exp_avg"]), state_fn(st["exp_avg_sq"])
+    group["params"][idx] = new_param
+    opt.state[new_param] = st
+    params[name] = new_param
+
+
 class Densifier:
     """``SplatfactoModel.refinement_after`` / ``split_gaussians`` / ``dup_gaussians`` / ``cull_gaussians`` and the
     optimiser-state surgery ``dup_in_optim`` / ``remove_from_optim`` (``street_gaussians_ns/sgn_splatfacto.py:459-511,
@@ -248,23 +269,10 @@ class Densifier:
         self.stats.update(xys_grad, radii, self.last_size, step=step)
 
     # ------------------------------------------------------------------------------------------ optimiser surgery
-    @staticmethod
-    def _leaf_like(old: torch.Tensor, data: torch.Tensor) -> torch.Tensor:
-        """A new autograd leaf of the kind ``old`` was (nn.Parameter, as the reference re-creates them, or plain)."""
-        return torch.nn.Parameter(data) if isinstance(old, torch.nn.Parameter) else data.requires_grad_(True)
+    _leaf_like = staticmethod(leaf_like)
 
     def _rebind(self, name: str, new_param: torch.Tensor, state_fn) -> None:
-        """Swap parameter ``name`` for ``new_param`` in its optimiser, transforming exp_avg / exp_avg_sq with
-        ``state_fn`` (:459-475, :483-504)."""
-        opt, old = self.optimizers[name], self.params[name]
-        group = opt.param_groups[0]
-        idx = next(i for i, p in enumerate(group["params"]) if p is old)
-        st = opt.state.pop(old, {})
-        if "exp_avg" in st:
-            st["exp_avg"], st["exp_avg_sq"] = state_fn(st["exp_avg"]), state_fn(st["exp_avg_sq"])
-        group["params"][idx] = new_param
-        opt.state[new_param] = st
-        self.params[name] = new_param
+        rebind(self.params, self.optimizers, name, new_param, state_fn)
 
     # ----------------------------------------------------------------------------------------------------- pieces
     def _split_noise(self, mask: torch.Tensor, n_splits: int, samps: int, step: int) -> torch.Tensor:

@@ -586,7 +586,8 @@ def train_step(P: Dict[str, torch.Tensor], cam: Camera, w_img: torch.Tensor, w_a
     ``absgrad=True`` (``fused=True`` only; ``ValueError`` otherwise): the colour pass sums the absolute screen-space
     gradients, ``out.xys.absgrad`` [N,2] after the backward.  ``densifier`` (a :class:`sgn_rast.densify.Densifier`):
     its ``after_train(step, ...)`` runs behind the backward with this render's ``xys.grad`` — or, under
-    ``DensifyConfig(absgrad=True)``, its ``xys.absgrad`` — radii and image size.
+    ``DensifyConfig(absgrad=True)``, its ``xys.absgrad`` — radii and image size; a densifier that has a
+    ``regularizer()`` (:class:`sgn_rast.mcmc.MCMCDensifier`) gets its value added to the loss.
     ``appearance=(grids, index)`` — a :class:`sgn_rast.appearance.BilateralGrids` module or its ``[num, L, Hg, Wg, 12]``
     tensor, and the image's (or sensor's) number — corrects ``out.rgb`` with ``appearance.slice_image`` after the sky
     composite and before the photometric loss, whose own clamp and mask then act on the corrected colour; the
@@ -664,6 +665,8 @@ def train_step(P: Dict[str, torch.Tensor], cam: Camera, w_img: torch.Tensor, w_a
             term = lidar.depth_loss(dsum, acc, lidar_depth, depth_loss_kind, mask)
             loss = loss + depth_loss_mult * term
             out.depth_loss = term.detach()
+    if hasattr(densifier, "regularizer"):     # sgn_rast.mcmc.MCMCDensifier: the opacity / scale regulariser
+        loss = loss + densifier.regularizer()
     if loss.requires_grad:        # an empty view (the reference's constant outputs) has nothing to differentiate
         loss.backward()
     if reducer is not None:
