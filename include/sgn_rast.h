@@ -1207,6 +1207,68 @@ int sgn_aa_opacity_fwd(int n, const float *opacity_logits, const float *compensa
 int sgn_aa_opacity_bwd(int n, const float *opacity_logits, const float *compensation, const float *v_opacities,
                        float *v_opacity_logits, float *v_compensation, sgn_stream_t stream);
 
+/* ROLLING SHUTTER (no upstream counterpart: the reference renders a global shutter).  The sensor reads line c of the
+ * shutter axis s (SGN_SHUTTER_ROWS: s = y, extent E = img_h; SGN_SHUTTER_COLS: s = x, E = img_w; o is the other axis)
+ * at time tau(c) = T * (c / E - 0.5) around the mid-exposure pose the projection ran at; pixel centres sit at r + 0.5,
+ * T < 0 reverses the readout.  `lin` = R (v_cam - v_obj) and `ang` = R w_cam are the camera's velocity relative to the
+ * row's object and its angular velocity, rotated into the CAMERA frame by the host (R = viewmat[:3,:3]); with
+ * object_ids / lin_table [n_objects, 3] the row's `lin` is lin_table[object_ids[i]] (an id outside the table reads its
+ * nearest row), else the struct's.  Per row with radii > 0, from the projection's (u, z, r, Q = [[q0, q1], [q1, q2]]),
+ * fp32, no contraction, every expression evaluated as written (left to right):
+ *   u    = u - margin                                  (both axes; the projection ran on a padded image, see below)
+ *   x    = (u_x - cx) * (z + 1e-6f) / fx               y = (u_y - cy) * (z + 1e-6f) / fy        p = (x, y, z)
+ *   pd   = -l - w x p:   pd_x = -l_x - (w_y * z - w_z * y),  pd_y = -l_y - (w_z * x - w_x * z),  pd_z = -l_z - (w_x * y - w_y * x)
+ *   a_x  = fx * (pd_x - (x / z) * pd_z) / z            a_y = fy * (pd_y - (y / z) * pd_z) / z    (screen velocity)
+ *   g    = a * T / E          k = 1.f - g_s            b = -g_o                A = I - g e_s^T
+ *   u'_s = (u_s - 0.5f * T * a_s) / k                  tau' = T * (u'_s / E - 0.5f)
+ *   u'_o = u_o + a_o * tau'                            depth' = z + pd_z * tau'
+ *   Q'   = A^T Q A:   Q'_oo = Q_oo,   Q'_os = Q_oo * b + q1 * k,   Q'_ss = b * Q'_os + k * (q1 * b + Q_ss * k)
+ *   c    = g_o / k,  d = 1.f + g_s / k,  t = 1.f + c * c + d * d                (A^-1 = I + g e_s^T / k)
+ *   sigma = sqrtf(0.5f * (t + sqrtf(fmaxf(0.f, t * t - 4.f * (d * d)))))        (its largest singular value)
+ *   r'   = (int)ceilf((float)r * sigma)                conservative: never below the sheared footprint's 3-sigma radius
+ *   num_tiles_hit' = the area of sgn tile bbox(u', r') on the REAL image's tile grid under `semantics`, as the projection
+ * A row is culled when k < 0.5f (the point nearly keeps pace with the shutter), depth' <= clip_thresh or the tile area
+ * is 0: xys', depths', radii', num_tiles_hit' are 0 as the projection writes them, conics' holds Q' (the projection
+ * writes its conic before the area test, too).  A row with radii <= 0 comes out culled with its conic unchanged.
+ * With l = w = 0 every product above is with an exact 0 or 1: k = 1, b = c = 0, sigma = 1, and — margin = 0 — all five
+ * outputs equal the inputs bit for bit; that only holds without contraction or reassociation (-ffp-contract=off).
+ * The compensation factor is not touched (and not an argument).
+ * `margin` m >= 0 (pixels): the caller ran the projection on a virtual image (img_h + 2 m, img_w + 2 m) with the
+ * principal point at (cx + m, cy + m), so that a Gaussian just off the image at mid-exposure survives to be moved onto
+ * the border lines; the struct carries the REAL img_h, img_w, cx, cy.  Side effects of m > 0: the projection's
+ * 1.3 * tan(fov / 2) Jacobian clamp is taken from the padded size, and u carries the rounding of adding and
+ * subtracting m (at most one ulp of img_w + 2 m on an unmoved row).
+ * sgn_rolling_shutter_bwd: the analytic vjp of the above with respect to (u, z, Q), including the dependence of a on u
+ * and z; the velocities are data.  radii_out is the forward's: a row culled there gets zero gradients.  v_depths_out
+ * may be NULL (no gradient arrives through the depths).
+ * One row per lane, 4-byte accesses: the arrays need no more than float alignment.  n == 0 returns 0 without a launch.
+ * Return codes: -1 n < 0; -2 rs or a required pointer is NULL; -3 axis is neither constant; -4 bad image size / block
+ * width (2..16); -5 fx or fy <= 0, margin < 0; -6 exactly one of object_ids / lin_table given, or n_objects < 1 with
+ * them.  csrc/rolling_shutter.hip. */
+#define SGN_SHUTTER_ROWS 0
+#define SGN_SHUTTER_COLS 1
+typedef struct sgn_shutter {
+    float fx, fy, cx, cy;    /* the real camera's intrinsics */
+    float lin[3];            /* R (v_cam - v_obj), used when lin_table is NULL */
+    float ang[3];            /* R w_cam */
+    float duration;          /* T, seconds, signed */
+    float margin;            /* m, pixels */
+    float clip_thresh;       /* the projection's */
+    int32_t axis;            /* SGN_SHUTTER_ROWS | SGN_SHUTTER_COLS */
+    int32_t img_h, img_w, block_width;
+    int32_t semantics;       /* SGN_SEM_* bits (the tile bbox's) */
+} sgn_shutter;
+int sgn_rolling_shutter_fwd(int n, const float *xys, const float *depths, const int32_t *radii, const float *conics,
+                            const int32_t *object_ids /*[n] or NULL*/, const float *lin_table /*[n_objects,3] or NULL*/,
+                            int n_objects, const sgn_shutter *rs, float *xys_out, float *depths_out,
+                            int32_t *radii_out, float *conics_out, int32_t *num_tiles_hit_out, sgn_stream_t stream);
+int sgn_rolling_shutter_bwd(int n, const float *xys, const float *depths, const float *conics,
+                            const int32_t *radii_out, const int32_t *object_ids /*[n] or NULL*/,
+                            const float *lin_table /*[n_objects,3] or NULL*/, int n_objects, const sgn_shutter *rs,
+                            const float *v_xys_out, const float *v_depths_out /*may be NULL*/,
+                            const float *v_conics_out, float *v_xys, float *v_depths, float *v_conics,
+                            sgn_stream_t stream);
+
 /* BILATERAL GRID (per-image colour correction: cameras of a street rig meter on their own; gsplat's trainer answers
  * with a bilateral grid per image, the original Street Gaussians code with a 3x4 affine per image / sensor, which is the
  * 1 x 1 x 1 grid).  grid: g[L, Hg, Wg, 12] float32, cell-major, coefficient 4 r + c = row r, column c of a 3x4 affine

@@ -173,6 +173,8 @@ SIGNATURES = {
     "sgn_depth_metrics": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sgn_aa_opacity_fwd": (_i, [_i, _vp, _vp, _vp, _vp]),
     "sgn_aa_opacity_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sgn_rolling_shutter_fwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sgn_rolling_shutter_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sgn_bilagrid_slice_fwd": (_i, [_i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "sgn_bilagrid_slice_bwd": (_i, [_i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
 }
@@ -222,6 +224,17 @@ class PanelDesc(C.Structure):
     """`sgn_panel` of include/sgn_rast.h: one panel of a frame-packing call (a host array of these is passed)."""
     _fields_ = [("src", C.c_void_p), ("lut", C.c_void_p), ("kind", C.c_int32), ("y0", C.c_int32), ("x0", C.c_int32),
                 ("invert", C.c_int32), ("lo", C.c_float), ("den", C.c_float)]
+
+
+SHUTTER_ROWS, SHUTTER_COLS = 0, 1      # SGN_SHUTTER_*
+
+
+class Shutter(C.Structure):
+    """`sgn_shutter` of include/sgn_rast.h: the rolling-shutter pass's per-call constants."""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("lin", C.c_float * 3),
+                ("ang", C.c_float * 3), ("duration", C.c_float), ("margin", C.c_float), ("clip_thresh", C.c_float),
+                ("axis", C.c_int32), ("img_h", C.c_int32), ("img_w", C.c_int32), ("block_width", C.c_int32),
+                ("semantics", C.c_int32)]
 
 
 # The library itself is stateless; the HOST keeps the options: one process-wide default object (library defaults,

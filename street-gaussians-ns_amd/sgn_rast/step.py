@@ -16,6 +16,7 @@ from typing import Dict, Optional
 import torch
 
 from . import ops as _hip_ops
+from . import shutter as _shutter
 from .quat import quaternion_multiply   # what `from pytorch3d.transforms import quaternion_multiply` resolves to
 from .scenes import Camera
 
@@ -72,13 +73,22 @@ def _split_recat(t: torch.Tensor, counts, retain_grad: bool = False):
 def render(P: Dict[str, torch.Tensor], cam: Camera, sh_degree_to_use: int = 3, block_width: int = 16,
            background: Optional[torch.Tensor] = None, with_depth: bool = False, ops=_hip_ops,
            retain_xys_grad: bool = True, split_counts=None, caller_syncs: bool = True,
-           rasterize_mode: str = "classic") -> SimpleNamespace:
+           rasterize_mode: str = "classic", rolling_shutter=None, object_velocities=None) -> SimpleNamespace:
     """``split_counts``: per-sub-model Gaussian counts when the caller is the scene graph (its property setters split
     and re-concatenate every projection output).  ``caller_syncs``: also replay the two host syncs the reference's
     own code performs per pass (`radii.sum() == 0` at :878, `assert (num_tiles_hit > 0).any()` at :944).
     ``rasterize_mode="antialiased"``: the opacities are the reference's own commented-out expression (:947),
-    ``torch.sigmoid(opacities) * comp[:, None]``, with autograd through the projection's compensation output."""
+    ``torch.sigmoid(opacities) * comp[:, None]``, with autograd through the projection's compensation output.
+    ``rolling_shutter`` (a :class:`sgn_rast.shutter.RollingShutter`; None: global shutter, today's path untouched): the
+    projection's outputs pass through :func:`sgn_rast.shutter.apply` directly behind the projection call, so ``out.xys``
+    and the other projection outputs — what the rasterizer, the depth pass, ``xys.grad`` and the scene graph's splits
+    see — are the sheared ones.  ``object_velocities`` [M,3] (with ``split_counts``: one row per sub-model, world
+    axes, zero for the background): each sub-model's Gaussians move with their own linear velocity.  Out of scope: the
+    per-line rotation of the SH view directions, object angular velocity, learnable velocities."""
     antialiased = antialiased_mode(rasterize_mode)
+    rs = _shutter.check(rolling_shutter)
+    if object_velocities is not None and (rs is None or split_counts is None):
+        raise ValueError("object_velocities needs rolling_shutter and the scene graph's split_counts")
     dev = P["means"].device
     H, W = cam.height, cam.width
     if background is None:
@@ -87,7 +97,16 @@ def render(P: Dict[str, torch.Tensor], cam: Camera, sh_degree_to_use: int = 3, b
     colors = torch.cat((P["features_dc"], P["features_rest"]), dim=1)            # :858
     quats = P["quats"] / P["quats"].norm(dim=-1, keepdim=True)                   # :864
     xys, depths, radii, conics, comp, num_tiles_hit, _cov3d = ops.project_gaussians(   # :860-873
-        P["means"], scales, 1, quats, cam.viewmat[:3, :], cam.fx, cam.fy, cam.cx, cam.cy, H, W, block_width)
+        P["means"], scales, 1, quats, cam.viewmat[:3, :], cam.fx, cam.fy, *_shutter.projection_frame(cam, rs),
+        block_width)
+    if rs is not None:
+        ids = None
+        if object_velocities is not None:
+            from .fused import object_ids_for
+            ids = object_ids_for(split_counts, dev)
+        xys, depths, radii, conics, num_tiles_hit = _shutter.apply(
+            xys, depths, radii, conics, num_tiles_hit, cam, rs, block_width, object_ids=ids,
+            object_velocities=object_velocities)
     out = SimpleNamespace()
     if split_counts is not None:                       # tuple-assign through the scene graph's setters, in order
         xys, out.xys_parts = _split_recat(xys, split_counts, retain_grad=retain_xys_grad)
@@ -135,7 +154,7 @@ def render_fused(P: Dict[str, torch.Tensor], cam: Camera, sh_degree_to_use: int 
                  object_ids: Optional[torch.Tensor] = None, poses: Optional[torch.Tensor] = None,
                  idft: Optional[torch.Tensor] = None, depth_channel: bool = True,
                  group_split: Optional[int] = None, rasterize_mode: str = "classic",
-                 absgrad: bool = False) -> SimpleNamespace:
+                 absgrad: bool = False, rolling_shutter=None, object_velocities=None) -> SimpleNamespace:
     """Same result as :func:`render` on the scene-graph-aggregated parameters, through the fused front
     ends (:mod:`sgn_rast.fused`): raw parameters in, no activation / concat / transform kernels.
     ``P["means"]`` / ``P["quats"]`` are in each object's LOCAL frame when ``object_ids``/``poses`` are given;
@@ -145,16 +164,30 @@ def render_fused(P: Dict[str, torch.Tensor], cam: Camera, sh_degree_to_use: int 
     same render — ``features.rasterize_features``, ``expected_depth`` — take with ``opacity_is_logit=False``).
     ``absgrad=True``: the COLOUR pass also sums the absolute screen-space gradients — ``out.xys.absgrad`` [N,2] after
     ``backward()`` (:func:`sgn_rast.fused.rasterize_gaussians_fused`); the separate depth pass of
-    ``depth_channel=False`` does not take part."""
+    ``depth_channel=False`` does not take part.
+    ``rolling_shutter`` (a :class:`sgn_rast.shutter.RollingShutter`; None: global shutter, today's path untouched): the
+    projection's outputs pass through :func:`sgn_rast.shutter.apply` directly behind the projection call; ``out.xys``
+    and the other projection outputs are its results, so the binning prefetch, every raster pass, ``xys.grad`` /
+    ``xys.absgrad`` and the antialiased opacities (the compensation factor passes through) work on the sheared
+    Gaussians.  ``object_velocities`` [M,3] (with ``object_ids`` / ``poses``; world axes, one row per pose-table entry,
+    zero for the background): each object's Gaussians move with their own linear velocity.  Out of scope: the per-line
+    rotation of the SH view directions, object angular velocity, learnable velocities."""
     from . import fused
     antialiased = antialiased_mode(rasterize_mode)
+    rs = _shutter.check(rolling_shutter)
+    if object_velocities is not None and (rs is None or object_ids is None):
+        raise ValueError("object_velocities needs rolling_shutter and object_ids / poses")
     dev = P["means"].device
     H, W = cam.height, cam.width
     if background is None:
         background = _zeros3(dev)
     xys, depths, radii, conics, comp, num_tiles_hit, _cov3d = fused.project_gaussians_fused(
-        P["means"], P["log_scales"], P["quats"], cam.viewmat[:3, :], cam.fx, cam.fy, cam.cx, cam.cy, H, W,
-        block_width, object_ids=object_ids, poses=poses)
+        P["means"], P["log_scales"], P["quats"], cam.viewmat[:3, :], cam.fx, cam.fy,
+        *_shutter.projection_frame(cam, rs), block_width, object_ids=object_ids, poses=poses)
+    if rs is not None:
+        xys, depths, radii, conics, num_tiles_hit = _shutter.apply(
+            xys, depths, radii, conics, num_tiles_hit, cam, rs, block_width,
+            object_ids=object_ids if object_velocities is not None else None, object_velocities=object_velocities)
     out = SimpleNamespace(xys=xys, depths=depths, radii=radii, conics=conics, num_tiles_hit=num_tiles_hit)
     if xys.requires_grad:
         xys.retain_grad()
@@ -297,7 +330,8 @@ def _submodel_raster(models, world_means, dcs, out, sub, cam: Camera, sh_degree_
 def render_scene_graph(models, poses: torch.Tensor, idft: torch.Tensor, cam: Camera, sh_degree_to_use: int = 3,
                        block_width: int = 16, ops=_hip_ops, fused: bool = False,
                        caller_syncs: bool = True, sh_parts: bool = True, groups: bool = True,
-                       rasterize_mode: str = "classic", absgrad: bool = False) -> SimpleNamespace:
+                       rasterize_mode: str = "classic", absgrad: bool = False, rolling_shutter=None,
+                       object_velocities=None) -> SimpleNamespace:
     """Replay of ``SplatfactoSceneGraphModel.get_outputs`` in training mode
     (``sgn_splatfacto_scene_graph.py:305-366``): ``models[0]`` is the background, ``models[i>0]`` rigid objects
     whose parameters live in the object's local frame; ``poses[i]`` = [R(9) t(3) q_o2w(4)], ``idft[i]`` = Fourier
@@ -308,8 +342,12 @@ def render_scene_graph(models, poses: torch.Tensor, idft: torch.Tensor, cam: Cam
     ``absgrad=True`` (fused path only; ``ValueError`` otherwise): the main colour pass sums the absolute screen-space
     gradients (:func:`render_fused`); after ``backward()``, ``out.xys_absgrad_parts()`` returns the per-sub-model
     slices of ``out.xys.absgrad`` in model order — what each sub-model's ``after_train`` reads under
-    ``DensifyConfig(absgrad=True)``.  The accumulation passes add nothing to it."""
+    ``DensifyConfig(absgrad=True)``.  The accumulation passes add nothing to it.
+    ``rolling_shutter`` / ``object_velocities`` [len(models), 3]: as :func:`render` / :func:`render_fused`, on both
+    paths — the main projection's outputs are sheared once, and every pass (depth, the two accumulations) reads them;
+    a moving object shears with its own velocity.  (:func:`render_scene_graph_eval` does not take them.)"""
     antialiased = antialiased_mode(rasterize_mode)
+    _shutter.check(rolling_shutter)
     if absgrad and not fused:
         raise ValueError("absgrad is not supported on the drop-in operators (gsplat 0.1.x surface): use fused=True")
     dev = models[0]["means"].device
@@ -324,7 +362,8 @@ def render_scene_graph(models, poses: torch.Tensor, idft: torch.Tensor, cam: Cam
         # False keeps the round-3 form, two more id-range passes, for A/B and for the tests
         out = render_fused(P, cam, sh_degree_to_use, block_width, with_depth=True, object_ids=object_ids,
                            poses=poses, idft=idft_p, group_split=counts[0] if groups else None,
-                           rasterize_mode=rasterize_mode, absgrad=absgrad)
+                           rasterize_mode=rasterize_mode, absgrad=absgrad, rolling_shutter=rolling_shutter,
+                           object_velocities=object_velocities)
         if absgrad:
             out.xys_absgrad_parts = lambda: torch.split(out.xys.absgrad, counts)
         if groups:
@@ -334,7 +373,8 @@ def render_scene_graph(models, poses: torch.Tensor, idft: torch.Tensor, cam: Cam
     else:
         P, world_means, dcs = _world_scene_params(models, poses, idft)
         out = render(P, cam, sh_degree_to_use, block_width, with_depth=True, ops=ops,   # :363
-                     split_counts=counts, caller_syncs=caller_syncs, rasterize_mode=rasterize_mode)
+                     split_counts=counts, caller_syncs=caller_syncs, rasterize_mode=rasterize_mode,
+                     rolling_shutter=rolling_shutter, object_velocities=object_velocities)
         if getattr(out, "empty", False):        # nothing visible: the sub-model passes return their empty outputs too
             out.object_acc = torch.zeros(H, W, device=dev)
             out.background_acc = torch.zeros(H, W, device=dev)
@@ -382,25 +422,27 @@ def _eval_nothing_visible(H: int, W: int, background: torch.Tensor, sky: Optiona
 
 def render_eval(P: Dict[str, torch.Tensor], cam: Camera, background: torch.Tensor, sky: Optional[torch.Tensor] = None,
                 sh_degree: int = 3, block_width: int = 16, fused: bool = True, ops=_hip_ops,
-                rasterize_mode: str = "classic") -> Dict[str, torch.Tensor]:
+                rasterize_mode: str = "classic", rolling_shutter=None) -> Dict[str, torch.Tensor]:
     """``SplatfactoModel.get_outputs`` as ``get_outputs_for_camera`` reaches it: ``self.training == False`` under
     ``torch.no_grad()`` — the full SH degree whatever the step (sgn_splatfacto.py:937-938), a sky image looked up without
     jitter (``sky`` [H,W,3], e.g. ``sgn_rast.sky.sky_color(base, ..., jitter=None)``; None: ``use_sky_sphere=False``) and
     the final ``rgb.clamp(0, 1)`` (:974-975).  Returns the reference's keys: ``rgb`` [H,W,3], ``accumulation`` [H,W,1],
     ``depth`` [H,W,1] and ``sky`` when given.  ``fused=False`` is the call-site replay on the drop-in operators (or the
     oracle's, ``ops``); ``fused=True`` the fused front ends with the depth channel riding in the colour pass.
-    ``rasterize_mode``: as :func:`render` / :func:`render_fused`."""
+    ``rasterize_mode``, ``rolling_shutter``: as :func:`render` / :func:`render_fused` (the sky image is NOT rotated per
+    line)."""
     antialiased_mode(rasterize_mode)
+    _shutter.check(rolling_shutter)
     H, W = cam.height, cam.width
     with torch.no_grad():
         if fused:
             out = render_fused(P, cam, sh_degree, block_width, background=background, with_depth=True,
-                               rasterize_mode=rasterize_mode)
+                               rasterize_mode=rasterize_mode, rolling_shutter=rolling_shutter)
             if bool(out.radii.sum() == 0):                                             # :878
                 return _eval_nothing_visible(H, W, background, sky)
         else:
             out = render(P, cam, sh_degree, block_width, background=background, with_depth=True, ops=ops,
-                         retain_xys_grad=False, rasterize_mode=rasterize_mode)
+                         retain_xys_grad=False, rasterize_mode=rasterize_mode, rolling_shutter=rolling_shutter)
             if getattr(out, "empty", False):
                 return _eval_nothing_visible(H, W, background, sky)
         rgb, alpha = _eval_finish(out.rgb, out.alpha, sky)
@@ -568,7 +610,8 @@ def train_step(P: Dict[str, torch.Tensor], cam: Camera, w_img: torch.Tensor, w_a
                ssim_lambda: float = 0.2, loss_fn=None, caller_syncs: bool = False, zero_grad: bool = True,
                mask: Optional[torch.Tensor] = None, lidar_depth: Optional[torch.Tensor] = None,
                depth_loss_mult: float = 0.1, depth_loss_kind: str = "l1", rasterize_mode: str = "classic",
-               absgrad: bool = False, densifier=None, step: int = 0, appearance=None, **fused_kw) -> SimpleNamespace:
+               absgrad: bool = False, densifier=None, step: int = 0, appearance=None, rolling_shutter=None,
+               **fused_kw) -> SimpleNamespace:
     """One "train-step image": project fwd -> SH fwd -> rasterize(return_alpha) fwd -> scalar loss ->
     full backward to means / log-scales / raw quats / opacity logits / SH coefficients (the metric's definition,
     SURVEY.md §8d: the operator sequence; ``caller_syncs=True`` adds the two host syncs of the reference's own model
@@ -593,8 +636,13 @@ def train_step(P: Dict[str, torch.Tensor], cam: Camera, w_img: torch.Tensor, w_a
     composite and before the photometric loss, whose own clamp and mask then act on the corrected colour; the
     uncorrected image is kept as ``out.rgb_raw``, the grids' gradient lands in ``grids.grad`` (this step does not reset
     it).  It needs ``gt`` (``ValueError`` before the render otherwise).  Out of scope: ``train_step_views``, the
-    scene-graph step and the data-parallel exchange of the grids' gradients do not take it."""
+    scene-graph step and the data-parallel exchange of the grids' gradients do not take it.
+    ``rolling_shutter`` (a :class:`sgn_rast.shutter.RollingShutter`): the render is the rolling sensor's
+    (:func:`render` / :func:`render_fused`); the LiDAR term, absgrad and the densifier read the sheared ``out.xys`` /
+    ``out.radii``.  Out of scope: ``train_step_views``, the per-line rotation of the sky lookup and of the SH view
+    directions, learnable velocities, and the data-parallel exchange (the pass has nothing to exchange)."""
     antialiased = antialiased_mode(rasterize_mode)
+    _shutter.check(rolling_shutter)
     if appearance is not None:
         from . import appearance as _appearance
         if gt is None:
@@ -632,10 +680,10 @@ def train_step(P: Dict[str, torch.Tensor], cam: Camera, w_img: torch.Tensor, w_a
             sky["base"].grad = None
     if fused:
         out = render_fused(P, cam, sh_degree_to_use, block_width, with_depth=with_depth, rasterize_mode=rasterize_mode,
-                           absgrad=absgrad, **fused_kw)
+                           absgrad=absgrad, rolling_shutter=rolling_shutter, **fused_kw)
     else:
         out = render(P, cam, sh_degree_to_use, block_width, with_depth=with_depth, ops=ops,
-                     caller_syncs=caller_syncs, rasterize_mode=rasterize_mode)
+                     caller_syncs=caller_syncs, rasterize_mode=rasterize_mode, rolling_shutter=rolling_shutter)
     if sky is not None:
         composite_sky(out, cam, sky["base"], sky["c2w"], train=sky.get("train", True), fused=fused,
                       sky_fn=sky.get("fn"))
